@@ -21,6 +21,7 @@ instantiated by capture() right after the capture, as torch does without it."""
 import contextlib
 
 import torch
+import torch.distributed as dist
 
 _KEEP = []
 
@@ -39,7 +40,18 @@ def new_graph():
 @contextlib.contextmanager
 def capture(g, **kw):
     """torch.cuda.graph(g, **kw), then the exec instantiated at once (with
-    keep_graph=True torch would instantiate at the first replay)."""
+    keep_graph=True torch would instantiate at the first replay).
+
+    With a process group up the capture runs in thread-local error mode unless
+    the caller chose one: the group's watchdog thread polls the events of the
+    eager collectives issued just before (the warm-up iterations'), and in the
+    default global mode such a call from another thread, landing inside the
+    capture, invalidates it -- the next launch on the capturing stream fails
+    and capture end reports its branches unjoined (the RCCL world-1 bench
+    child's abort, about one run in three).  The capturing
+    thread's own calls are checked as before."""
+    if dist.is_available() and dist.is_initialized():
+        kw.setdefault("capture_error_mode", "thread_local")
     with torch.cuda.graph(g, **kw):
         yield g
     g.instantiate()

@@ -18,6 +18,15 @@ window's wall time.
 
 mode env: the env alone (random actions), for the sim-kernel roofline.
 
+A plain run sets up, warms up, times the `--steps` iterations and prints the
+headline line (`value`, `ms_per_step`, and what follows from the window
+alone).  `--full` adds every secondary measurement and check after the
+window: the measured round, the kernel and roofline timings, the fp32 / alias
+TD7 variants, `sync_rounds`, `reference_schedule`, the weight and replica
+checks and the CPU baseline.  `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy; the inputs are seeded, the same in every run
+of the same arguments.
+
 Multi-GPU: one process per GPU (torchrun); envs shard with no exchange,
 TD7 gradients are all-reduced over RCCL (weak scaling).  On RCCL the trainer
 replays the iterations with the collectives captured in the graphs, the
@@ -166,6 +175,15 @@ def parse():
                     help="skip the synchronous-round comparison of the async-episode loop (configs[1])")
     ap.add_argument("--no-reference-schedule", action="store_true",
                     help="skip the reference-schedule sub-line (RefScheduleTrainer, train mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also run every secondary measurement and check: the measured "
+                         "round, the kernel / roofline timings, the TD7 variants, the synchronous rounds, the "
+                         "reference schedule, the weight and replica checks and the CPU baseline (each with its "
+                         "own --no-* switch).  Without it the run sets up, warms up, times --steps iterations "
+                         "and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (the env outputs and, in train "
+                         "mode, the networks' weights) as DIR/<name>.npy, float32 / float64, rank 0")
     a = ap.parse_args()
     if a.envs is None:
         a.envs = {"configs1": 4096, "dr_sweep": 16384, "wide": 65536}[a.workload]
@@ -613,6 +631,26 @@ def td7_variants(env, dev, args, iters=60, warmup=8):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 * 2 ** 20  # all of --dump-outputs' files together (under 64 MB)
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: each tensor as path/<name>.npy (float64 stays, every
+    other dtype as float32).  The byte budget is shared evenly; an array over
+    its share is written as a fixed sample of its flattened elements (sorted
+    indices drawn without replacement from numpy's default_rng(0): the same
+    elements in every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(tensors), 1)
+    for name, t in tensors.items():
+        t = t.detach()
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -634,6 +672,11 @@ def main():
             dist.init_process_group(backend)
     from exo_amd import VecExoskeletonEnv
 
+    # the same inputs in every run of the same arguments: the initial weights
+    # (rank 0's are broadcast), the device RNG streams of the replay sampling
+    # and the policy noise (ops.DeviceRNG follows torch's seed) and env mode's
+    # random actions
+    torch.manual_seed(1000 + rank)
     N = args.envs
     env_kw = {}
     if args.workload == "dr_sweep":  # per-env DR draws
@@ -878,14 +921,32 @@ def main():
     if clock is not None:
         window_clock = env.step_clock_ms()
         env.set_step_clock(False)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back, before anything else touches it:
+        # the env's outputs (train mode: the buffers the trainer's last rollout
+        # wrote, in-place episode resets included) and the updated networks
+        if trainer is not None:
+            o = trainer._outs[trainer._cur ^ 1]
+            nets = {n: torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+                    for n, m in (("actor", agent.learner.actor), ("critic", agent.learner.critic),
+                                 ("encoder", agent.learner.encoder))}
+        else:
+            o, nets = out, {}
+        dump_outputs(args.dump_outputs, {"obs": o[0], "reward": o[1], "done": o[2], "info": o[3], **nets})
+    # Everything below the window that takes runs of its own is --full's, except
+    # where the headline value is defined through it: synchronous episodes (and
+    # env mode) price the round's reset, a budgeted synchronous round is the
+    # measured round itself.
     # async episodes: no rounds (every env resets in place inside the timed
     # iterations), the window itself is the whole-job rate
-    measured_round = measured_round_timing() if trainer is not None else None
-    reset_ms = reset_timing()
-    loop_kern_ms = None
+    measured_round = None
+    if trainer is not None and (args.full or (trainer.budget and not async_eps)):
+        measured_round = measured_round_timing()
+    reset_ms = reset_timing() if args.full or not async_eps else None
+    loop_kern_ms = kern_ms = kern_active = None
     if ev:  # env mode: the timed launches themselves
         kern_ms, kern_active = float(np.mean([a.elapsed_time(b) for a, b in ev])), env_steps / args.steps
-    else:   # train mode: the env kernel is inside graph replays; time it separately afterwards
+    elif args.full:  # train mode: the env kernel is inside graph replays; time it separately afterwards
         # the roofline kernel: the env step's default shape alone (the shape
         # profiles/*_env kernel stats time); a trainer that runs another shape
         # (EXO_TRAIN_STEP_SHARED=1: rows_shared) has it timed alone too, reported with it
@@ -918,8 +979,9 @@ def main():
     # t_iter = the window's time per iteration with any resets it contained
     # taken out; value = A_round / (round_len * t_iter + t_reset), summed over
     # ranks (max of the ranks' times).
-    t = torch.tensor([elapsed, float(env_steps), (elapsed - resets_in_window * reset_ms * 1e-3) / args.steps,
-                      reset_ms * 1e-3], device=dev, dtype=torch.float64)
+    reset_s = (reset_ms or 0.0) * 1e-3  # (not timed: async episodes, whose value does not use it)
+    t = torch.tensor([elapsed, float(env_steps), (elapsed - resets_in_window * reset_s) / args.steps, reset_s],
+                     device=dev, dtype=torch.float64)
     if dist_on:
         tmax, tsum = t.clone(), t.clone()
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -938,28 +1000,29 @@ def main():
         # the whole measured round is the value
         round_value = world * measured_round[1] / measured_round[0]
     finite = None
-    if agent is not None:
+    if agent is not None and args.full:
         finite = {n: bool(torch.isfinite(torch.cat([p.detach().reshape(-1) for p in m.parameters()])).all())
                   for n, m in (("actor", agent.learner.actor), ("critic", agent.learner.critic),
                                ("encoder", agent.learner.encoder))}
     dp_sync = dp_ck = dp_lay_ranks = None
     ref_sched = None
-    if agent is not None and args.mode == "train" and not args.no_reference_schedule:
+    if args.full and agent is not None and args.mode == "train" and not args.no_reference_schedule:
         # every rank (collectives inside); rank 0 reports
         ref_sched = reference_schedule(env, dev, args, agent.hp, group=dist.group.WORLD if dist_on else None)
     sync_cmp = None
-    if (agent is not None and args.mode == "train" and async_eps and args.workload == "configs1"
+    if (args.full and agent is not None and args.mode == "train" and async_eps and args.workload == "configs1"
             and not args.no_sync_rounds):
         sync_cmp = sync_rounds(env, dev, args, agent.hp, group=dist.group.WORLD if dist_on else None)
     if agent is not None and dist_on:
-        # data-parallel replicas must hold bit-identical weights
-        ck = torch.stack([torch.cat([p.detach().reshape(-1) for p in m.parameters()]).double().sum()
-                          for m in (agent.learner.actor, agent.learner.critic, agent.learner.encoder)]
-                         + [agent.replay_buffer._maxp.double().reshape(())])  # and the global max_priority
-        allck = [torch.zeros_like(ck) for _ in range(world)]
-        dist.all_gather(allck, ck)
-        dp_sync = all(torch.equal(allck[0], x) for x in allck)
-        dp_ck = [x.tolist() for x in allck]
+        if args.full:
+            # data-parallel replicas must hold bit-identical weights
+            ck = torch.stack([torch.cat([p.detach().reshape(-1) for p in m.parameters()]).double().sum()
+                              for m in (agent.learner.actor, agent.learner.critic, agent.learner.encoder)]
+                             + [agent.replay_buffer._maxp.double().reshape(())])  # and the global max_priority
+            allck = [torch.zeros_like(ck) for _ in range(world)]
+            dist.all_gather(allck, ck)
+            dp_sync = all(torch.equal(allck[0], x) for x in allck)
+            dp_ck = [x.tolist() for x in allck]
         # every rank's layout: in-graph collectives, overlapped pairs
         lay = torch.tensor([float(trainer.dp_inline) if trainer is not None else -1.0,
                             float(any(isinstance(k, tuple) and k[-1] == "overlap" for k in trainer.graphs))
@@ -968,9 +1031,6 @@ def main():
         dist.all_gather(all_lay, lay)
         dp_lay_ranks = [x.tolist() for x in all_lay]
     if rank == 0:
-        active_avg = kern_active
-        achieved = BYTES_PER_ENV_STEP * active_avg / (kern_ms * 1e-3) / 1e9
-        traffic, traffic_src = pmc_traffic(float(BYTES_PER_ENV_STEP * active_avg))
         res = {
             "metric": "env steps/sec (batched exo sim) + TD7 grad-steps/sec at 1/2/4/8 MI355X",
             "value": round_value,
@@ -1009,17 +1069,24 @@ def main():
                                         "async episodes round_len consecutive iterations with their in-place "
                                         "resets"}
                                if measured_round else None),
-            "env_kernel_env_steps_per_sec": active_avg / (kern_ms * 1e-3),
-            "reset_kernel_ms": reset_ms,  # one reset of every env (exo_reset_kernel), HIP events
-            "roofline": {"kernel": ("exo_step_rp_kernel" if N <= 16384 else "exo_step_kernel")
-                                   + (" + exo_multibody_kernel" if args.physics == "multibody" else ""), "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": BYTES_PER_ENV_STEP * active_avg,
-                         "bytes_per_env_step": BYTES_PER_ENV_STEP, "avg_kernel_ms": kern_ms,
-                         "active_envs_per_launch": active_avg},
+            "full": args.full,
         }
-        if ev == [] and agent is not None:
+        if reset_ms is not None:
+            res["reset_kernel_ms"] = reset_ms  # one reset of every env (exo_reset_kernel), HIP events
+        if kern_ms is not None:  # env mode: the timed launches' own events; train mode: --full's kernel timings
+            active_avg = kern_active
+            achieved = BYTES_PER_ENV_STEP * active_avg / (kern_ms * 1e-3) / 1e9
+            traffic, traffic_src = pmc_traffic(float(BYTES_PER_ENV_STEP * active_avg))
+            res["env_kernel_env_steps_per_sec"] = active_avg / (kern_ms * 1e-3)
+            res["roofline"] = {"kernel": ("exo_step_rp_kernel" if N <= 16384 else "exo_step_kernel")
+                                         + (" + exo_multibody_kernel" if args.physics == "multibody" else ""),
+                               "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "traffic_unit": "bytes per launch", "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": BYTES_PER_ENV_STEP * active_avg,
+                               "bytes_per_env_step": BYTES_PER_ENV_STEP, "avg_kernel_ms": kern_ms,
+                               "active_envs_per_launch": active_avg}
+        if ev == [] and agent is not None and kern_ms is not None:
             res["roofline"]["measured_on"] = ("default shape alone, all envs active, U(-1, 1) actions"
                                               if args.workload == "configs1" else
                                               "the timed window's own step launches inside the graph-replayed "
@@ -1044,7 +1111,8 @@ def main():
                 "variant": env.step_variant, "avg_kernel_ms_alone": loop_kern_ms,
                 "note": "32 envs per 512-thread workgroup: half the CUs at 4,096 envs, so the fused TD7 "
                         "workgroups beside it keep whole CUs (DESIGN.md 4)"}
-        vfl, vsrc = pmc_valu_flops(N) if args.physics == "ideal" and N <= 16384 else (None, None)
+        vfl, vsrc = (pmc_valu_flops(N) if kern_ms is not None and args.physics == "ideal" and N <= 16384
+                     else (None, None))
         if vfl and kern_active == N:
             # the env kernel is fp64-VALU/latency bound -- its
             # compute fraction next to the HBM one (flops: PMC, issued lanes)
@@ -1061,7 +1129,7 @@ def main():
                     "issued_over_useful": vfl / (uf * N), "rk45_attempts_per_env_step": att, "attempts_source": usrc,
                     "model": "bench.py USEFUL_FLOPS: the step's arithmetic once per env (a scalar implementation "
                              "of the kernel's algorithm), counted by hand"}
-        if args.physics == "multibody":
+        if args.physics == "multibody" and args.full:
             # q, qd of 19 joints read + written (f64), 5 targets, 1 flag byte read + cleared
             mb_ms = multibody_timing()
             res["multibody_kernel"] = {"kernel": "exo_multibody_kernel", "avg_kernel_ms": mb_ms,
@@ -1096,6 +1164,7 @@ def main():
                                               "over all envs (bench.td7_flops)",
                                    "note": "GEMM flops of one train() step (B=8x128) + batched actor inference "
                                            "over the envs, per whole iteration time (env step included: a lower bound)"}
+        if agent is not None and args.full:  # the two critic kernels alone, each in a graph of its own
             us, cfl = critic_gemm_timing(agent)
             res["critic_gemm_roofline"] = {
                 "kernel": "td7_dense_fwd, critic Linear(2*zs+h -> h) + ELU, both Q heads", "bound": "mfma",
@@ -1117,9 +1186,10 @@ def main():
                     "mfma": {"achieved": fc["flop"] / (fc["us"] * 1e-6) / 1e12, "peak": peak, "unit": "TFLOP/s",
                              "frac": fc["flop"] / (fc["us"] * 1e-6) / 1e12 / peak, "flop_per_launch": fc["flop"]},
                     "peak_source": "tools/stream_bench.hip (profiles/r02b_raw/stream_bench.txt)"}
-        if agent is not None and args.workload == "configs1" and world == 1 and not args.no_td7_variants:
+        if (args.full and agent is not None and args.workload == "configs1" and world == 1
+                and not args.no_td7_variants):
             res["td7_variants"] = td7_variants(env, dev, args)
-        if dp_sync is not None:
+        if dp_lay_ranks is not None:
             res["dp_layout"] = dp_layout(trainer)
             res["dp_layout_per_rank"] = [("one graph, collectives captured (RCCL)" if a == 1.0 else
                                           "three graphs, eager collectives") for a, _ in dp_lay_ranks]
@@ -1139,7 +1209,7 @@ def main():
             res["dp_weights_in_sync"] = dp_sync
             if not dp_sync:
                 res["dp_weight_checksums"] = dp_ck
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             td7 = None
             if agent is not None:
                 td7 = (agent.hp, agent.hp.batch_size * agent.env_num, total_env_steps / args.steps)

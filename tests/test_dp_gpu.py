@@ -34,7 +34,7 @@ def test_two_rank_training_keeps_replicas_in_sync():
     env = dict(os.environ, EXO_BENCH_DEVICE="0", EXO_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "12", "--warmup", "6", "--envs", "256", "--no-cpu-baseline",
+           "--gpus", "2", "--steps", "12", "--warmup", "6", "--envs", "256", "--full", "--no-cpu-baseline",
            "--kernel-timing-steps", "5"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-4000:]
@@ -78,7 +78,7 @@ def test_rccl_data_parallel_layout_at_world_one():
     env.pop("EXO_DIST_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr=127.0.0.1", f"--master-port={_port()}", os.path.join(REPO, "bench.py"),
-           "--steps", "20", "--warmup", "8", "--envs", "512", "--no-cpu-baseline", "--no-td7-variants",
+           "--steps", "20", "--warmup", "8", "--envs", "512", "--full", "--no-cpu-baseline", "--no-td7-variants",
            "--no-reference-schedule", "--kernel-timing-steps", "5"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, _failure_text(out, "rccl_world1_bench_child")
