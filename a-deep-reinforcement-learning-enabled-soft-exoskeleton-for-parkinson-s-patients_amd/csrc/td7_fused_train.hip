@@ -22,6 +22,7 @@
 // the same lanes).  Bias gradients come from the unrounded fp32 dP (column
 // partials per row tile, summed in td7f_wgrad).
 #include "td7_fused.h"
+#include "td7_xcd_map.h"
 #include "adam_math.h"
 
 #include <algorithm>
@@ -559,6 +560,9 @@ struct WgJob {
     long w_off, b_off;
     u32x4 *wf, *wb;
     int ksf, ksb, opt;
+    // dW (and p / m / v) of this job as 16-byte row accesses: K % 4 == 0 and
+    // 16-byte aligned bases; otherwise one dword per lane in the accumulator layout
+    int vec;
 };
 struct WgOpt {
     float *p, *m, *v, *step;
@@ -578,6 +582,7 @@ struct WgArgs {
     WgOpt o[TD7_ADAM_MAX_OPT];
     int nopt;
     uint32_t *ticket;
+    int xcd;  // tiles in XCD-contiguous order (td7_xcd_map.h); 0: blockIdx.x order
 };
 
 constexpr int PD2 = 8;  // k-steps (32 rows) in flight; the reduction length is a multiple of 32 PD2
@@ -585,45 +590,34 @@ constexpr int PD2 = 8;  // k-steps (32 rows) in flight; the reduction length is 
 // ADAM: the optimiser step of every weight / bias the launch differentiates
 // (adam_one, bit-identical to td7_adam_step_multi) and the repack of the
 // updated weights (bit-identical to td7f_pack) in the epilogue: the tile's p /
-// m / v are loaded before the k-loop (their latency hides under the MFMAs),
-// the updated 16-bit weights are staged in LDS and written out as whole forward
-// and dX items.  The optimiser step counts advance once (last workgroup out).
+// m / v loads are issued after the first PD2 operand k-steps (vmcnt retires in
+// issue order: issued before them, the first MFMA would wait for the last of
+// these loads), the updated weights are staged in LDS and written out as whole
+// forward and dX items.  The optimiser step counts advance once (last
+// workgroup out).
+// Tile order: the tiles that share a dP^T or X^T panel are neighbours in the
+// job / n-block / k-tile order; a.xcd gives every XCD (one L2) a contiguous
+// run of that order instead of every 8th tile.
+// J.vec: the gradient tile goes through an fp32 LDS image, and dW / p / m / v
+// move as 16-byte row accesses (a wave instruction covers four whole 256-byte
+// row segments); the values and adam_one's inputs are those of the scalar path.
 template <int P, bool ADAM>
-__global__ __launch_bounds__(256) void wgrad_kernel(WgArgs a) {
+__global__ __launch_bounds__(256, 2) void wgrad_kernel(WgArgs a) {
     if ((int)blockIdx.x == a.total) {
         for (int b = threadIdx.x; b < a.B; b += 256)
             stg(a.prio + b, powf(fmaxf(fmaxf(ldg(a.td + 2 * b), ldg(a.td + 2 * b + 1)), a.minp), a.alpha));
     } else {
+    const int b = a.xcd ? xcd_contiguous((int)blockIdx.x, a.total) : (int)blockIdx.x;
     int q = 0;
-    while (q + 1 < a.njobs && (int)blockIdx.x >= a.j[q + 1].first) ++q;
+    while (q + 1 < a.njobs && b >= a.j[q + 1].first) ++q;
     const WgJob &J = a.j[q];
-    const int t = blockIdx.x - J.first;
+    const int t = b - J.first;
     const int n0 = (t / J.tiles_k) * 64, k0 = (t % J.tiles_k) * 64;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wn = n0 + 32 * (w >> 1), wk = k0 + 32 * (w & 1);
+    // J.vec: this thread's 4 x 4 elements, rows vr + 16 h, columns vc .. vc + 3
+    const int vr = threadIdx.x >> 4, vc = 4 * (threadIdx.x & 15);
     const long ld = a.ld;
-    float ss = 0.f, bc = 1.f;
-    float pp[2][2][4], mm[2][2][4], vv[2][2][4], bp = 0.f, bm = 0.f, bv = 0.f;
-    if constexpr (ADAM) {
-        const WgOpt &o = a.o[J.opt];
-        const float st = *o.step + 1.0f;
-        ss = o.lr / (1.0f - powf(o.b1, st));
-        bc = sqrtf(1.0f - powf(o.b2, st));
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int v = 0; v < 2; ++v)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int n = wn + 16 * u + 4 * (lane >> 4) + e, k = wk + 16 * v + (lane & 15);
-                    const long i = J.w_off + ((n < J.N && k < J.K) ? (long)n * J.K + k : 0);
-                    pp[u][v][e] = ldg(o.p + i), mm[u][v][e] = ldg(o.m + i), vv[u][v][e] = ldg(o.v + i);
-                }
-        if (k0 == 0 && J.db && w == 0) {
-            const long i = J.b_off + (n0 + lane < J.N ? n0 + lane : 0);
-            bp = ldg(o.p + i), bm = ldg(o.m + i), bv = ldg(o.v + i);
-        }
-    }
     // the operands are in fragment blocks (td7_fused.h blk8 / blk4): the
     // fragment of operand rows g*16.. and k-step s (KD batch rows) is the 1 KiB
     // block g * (ld / KD) + s; they are padded to multiples of 64 rows (zeros),
@@ -652,6 +646,47 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgArgs a) {
             fb[p][u] = ldg((const u32x4 *)(bp2[u] + 1024 * p));
             __builtin_amdgcn_sched_barrier(0);
         }
+    // the tile's Adam state, behind the ring in the load queue.  Scalar path:
+    // accumulator layout, index (2u + v) * 4 + e; J.vec: row layout, 4h + j
+    float ss = 0.f, bc = 1.f;
+    float pp[16], mm[16], vv[16], bp = 0.f, bm = 0.f, bv = 0.f;
+    if constexpr (ADAM) {
+        const WgOpt &o = a.o[J.opt];
+        if (J.vec) {
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const int n = n0 + vr + 16 * h, k = k0 + vc;
+                floatx4 p4{0.f, 0.f, 0.f, 0.f}, m4 = p4, v4 = p4;
+                if (n < J.N && k < J.K) {
+                    const long i = J.w_off + (long)n * J.K + k;
+                    p4 = ldg((const floatx4 *)(o.p + i)), m4 = ldg((const floatx4 *)(o.m + i));
+                    v4 = ldg((const floatx4 *)(o.v + i));
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pp[4 * h + j] = p4[j], mm[4 * h + j] = m4[j], vv[4 * h + j] = v4[j];
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int v = 0; v < 2; ++v)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int n = wn + 16 * u + 4 * (lane >> 4) + e, k = wk + 16 * v + (lane & 15);
+                        const long i = J.w_off + ((n < J.N && k < J.K) ? (long)n * J.K + k : 0);
+                        const int x = (2 * u + v) * 4 + e;
+                        pp[x] = ldg(o.p + i), mm[x] = ldg(o.m + i), vv[x] = ldg(o.v + i);
+                    }
+        }
+        if (k0 == 0 && J.db && w == 0) {
+            const long i = J.b_off + (n0 + lane < J.N ? n0 + lane : 0);
+            bp = ldg(o.p + i), bm = ldg(o.m + i), bv = ldg(o.v + i);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        const float st = *o.step + 1.0f;
+        ss = o.lr / (1.0f - powf(o.b1, st));
+        bc = sqrtf(1.0f - powf(o.b2, st));
+    }
     int s0 = 0;
     for (; s0 + PD2 < ns; s0 += PD2) {
 #pragma unroll
@@ -683,6 +718,45 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgArgs a) {
     // C[n][k]: lane holds n = 16u + 4(lane >> 4) + e, k = 16v + (lane & 15)
     // the tile's updated weights in the operand type (rows padded to 144 / 272 B)
     __shared__ alignas(16) typename Ty<P>::E T[ADAM ? 64 : 1][Ty<P>::EB == 4 ? 68 : 72];
+    // J.vec: the tile's gradients (rows of 272 B: the four 16-lane groups of a
+    // wave's dword stores, 4 rows apart, fall in four different bank groups)
+    __shared__ alignas(16) float G[64][68];
+    if (J.vec) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    G[wn - n0 + 16 * u + 4 * (lane >> 4) + e][wk - k0 + 16 * v + (lane & 15)] =
+                        acc[u][v][e] * (1.f / Ty<P>::gs);
+        __syncthreads();
+#pragma unroll
+        for (int h = 0; h < 4; ++h) {
+            const int r = vr + 16 * h, n = n0 + r, k = k0 + vc;
+            const bool ok = n < J.N && k < J.K;  // K % 4 == 0: the four columns are in or out together
+            const floatx4 g4 = *(const floatx4 *)&G[r][vc];
+            if (ok) stg((floatx4 *)(J.dw + (long)n * J.K + k), g4);
+            if constexpr (ADAM) {
+                const WgOpt &o = a.o[J.opt];
+                float pw[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int x = 4 * h + j;
+                    adam_one(pp[x], g4[j], mm[x], vv[x], ss, bc, o.b1, o.b2, o.eps, o.wd, 1.0f);
+                    pw[j] = ok ? pp[x] : 0.f;
+                }
+                if (ok) {
+                    const long i = J.w_off + (long)n * J.K + k;
+                    stg((floatx4 *)(o.p + i), floatx4{pp[4 * h], pp[4 * h + 1], pp[4 * h + 2], pp[4 * h + 3]});
+                    stg((floatx4 *)(o.m + i), floatx4{mm[4 * h], mm[4 * h + 1], mm[4 * h + 2], mm[4 * h + 3]});
+                    stg((floatx4 *)(o.v + i), floatx4{vv[4 * h], vv[4 * h + 1], vv[4 * h + 2], vv[4 * h + 3]});
+                }
+                if constexpr (Ty<P>::EB == 4) *(floatx4 *)&T[r][vc] = floatx4{pw[0], pw[1], pw[2], pw[3]};
+                else *(u32x2 *)&T[r][vc] = pack4<P>(pw);
+            }
+        }
+    } else {
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -696,15 +770,17 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgArgs a) {
                 if (ok) stg(J.dw + (long)n * J.K + k, g);
                 if constexpr (ADAM) {
                     const WgOpt &o = a.o[J.opt];
-                    adam_one(pp[u][v][e], g, mm[u][v][e], vv[u][v][e], ss, bc, o.b1, o.b2, o.eps, o.wd, 1.0f);
+                    const int x = (2 * u + v) * 4 + e;
+                    adam_one(pp[x], g, mm[x], vv[x], ss, bc, o.b1, o.b2, o.eps, o.wd, 1.0f);
                     if (ok) {
                         const long i = J.w_off + (long)n * J.K + k;
-                        stg(o.p + i, pp[u][v][e]), stg(o.m + i, mm[u][v][e]), stg(o.v + i, vv[u][v][e]);
+                        stg(o.p + i, pp[x]), stg(o.m + i, mm[x]), stg(o.v + i, vv[x]);
                     }
-                    T[n - n0][k - k0] = Ty<P>::bits(ok ? pp[u][v][e] : 0.f);
+                    T[n - n0][k - k0] = Ty<P>::bits(ok ? pp[x] : 0.f);
                 }
             }
         }
+    }
     if (k0 == 0 && J.db) {
         // db[n] = sum of the row-tile partials: the 4 waves take every 4th
         // tile (independent loads in flight), then one LDS reduction
@@ -801,6 +877,14 @@ using namespace td7f;
 
 static XT xt_of(const td7f_xt &x) { return XT{x.x, x.dp, x.part}; }
 
+// a switch that is on unless the variable is "0"; read per call (the tests and
+// the A/Bs switch them): EXO_WGRAD_XCD (tiles in XCD-contiguous order),
+// EXO_WGRAD_VEC (16-byte dW / Adam accesses)
+static bool env_on(const char *name) {
+    const char *e = getenv(name);
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+static bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 static bool prec_ok(int p) { return p == PREC_BF16 || p == PREC_F16 || p == PREC_F32; }
 static bool xt_ok(const td7f_xt *xt, int n) {
     for (int i = 0; i < n; ++i)
@@ -1053,6 +1137,7 @@ static int wgrad_args(int32_t prec, int32_t njobs, const td7f_wg_job *jobs, int6
     g.njobs = njobs;
     g.ld = ld;
     g.rows = rows;
+    const bool vec = env_on("EXO_WGRAD_VEC");
     int total = 0;
     for (int q = 0; q < njobs; ++q) {
         const td7f_wg_job &J = jobs[q];
@@ -1068,9 +1153,11 @@ static int wgrad_args(int32_t prec, int32_t njobs, const td7f_wg_job *jobs, int6
         w.tiles_k = (J.k + 63) / 64;
         w.ntiles_rows = J.row_tiles;
         w.first = total;
+        w.vec = vec && J.k % 4 == 0 && al16(J.dw);
         total += ((J.n + 63) / 64) * w.tiles_k;
     }
     g.total = total;
+    g.xcd = env_on("EXO_WGRAD_XCD");
     g.td = td;
     g.prio = prio;
     g.B = B;
@@ -1117,6 +1204,8 @@ int td7f_wgrad_adam(int32_t prec, int32_t njobs, const td7f_wg_job *jobs, int64_
         WgJob &w = g.j[q];
         w.w_off = A.w_off;
         w.b_off = A.b_off;
+        const WgOpt &o = g.o[A.opt];
+        w.vec = w.vec && A.w_off % 4 == 0 && al16(o.p) && al16(o.m) && al16(o.v);
         w.wf = (u32x4 *)A.wf;
         w.wb = (u32x4 *)A.wb;
         w.ksf = A.ksf;
