@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <string>
 
+#include "lap_chain.h"
 #include "philox.h"
 #include "exo_amd.h"
 
@@ -1352,6 +1353,69 @@ struct TdPrio {
     float *out;
 };
 
+// lap_update_sample's own gather (EXO_LAP_GATHER_SPLIT=0): the rows pick[0 .. batch)
+// of stratum s, by the whole workgroup.
+__device__ __forceinline__ void gather_picked(const lap_storage_desc &st, int capacity, int s, int batch,
+                                              const int32_t *pick, float *o_state, float *o_action, float *o_next,
+                                              float *o_reward, float *o_not_done) {
+    // gather: (draw, item) over the workgroup, items = state, next_state (float4
+    // where the rows are 16-byte aligned), action, reward, not_done; GU items
+    // per thread loaded before any is stored (the stores may alias the loads as
+    // far as the compiler knows: item by item, every load would wait for the
+    // previous store -- r04 first cut, 54 us per launch)
+    const int sd = st.state_dim, ad = st.action_dim;
+    const bool v4 = (sd & 3) == 0 && ((reinterpret_cast<uintptr_t>(st.state) | reinterpret_cast<uintptr_t>(st.next_state) |
+                                       reinterpret_cast<uintptr_t>(o_state) | reinterpret_cast<uintptr_t>(o_next)) & 15) == 0;
+    const int sv = v4 ? sd / 4 : sd, per = 2 * sv + ad + 2;
+    const int items = min(batch, UPD_THREADS) * per;
+    constexpr int GU = 8;
+    for (int it0 = threadIdx.x; it0 < items; it0 += GU * UPD_THREADS) {
+        float4 v[GU];
+        float *dst[GU];
+        bool wide[GU];
+#pragma unroll
+        for (int u = 0; u < GU; ++u) {
+            const int it = it0 + u * UPD_THREADS;
+            dst[u] = nullptr;
+            wide[u] = false;
+            if (it >= items) continue;
+            const int b = it / per, c = it - b * per;
+            const long d = (long)s * batch + b;
+            const long row = (long)s * (capacity + 1) + pick[b];
+            if (c < 2 * sv) {
+                const bool nx = c >= sv;
+                const int e = nx ? c - sv : c;
+                const float *src = (nx ? st.next_state : st.state) + row * sd;
+                float *o = (nx ? o_next : o_state) + d * sd;
+                if (v4) {
+                    v[u] = ld4(src + 4 * e);
+                    dst[u] = o + 4 * e;
+                    wide[u] = true;
+                } else {
+                    v[u].x = src[e];
+                    dst[u] = o + e;
+                }
+            } else if (c < 2 * sv + ad) {
+                const int e = c - 2 * sv;
+                v[u].x = st.action[row * ad + e];
+                dst[u] = o_action + d * ad + e;
+            } else if (c == 2 * sv + ad) {
+                v[u].x = st.reward[row];
+                dst[u] = o_reward + d;
+            } else {
+                v[u].x = st.not_done[row];
+                dst[u] = o_not_done + d;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < GU; ++u) {
+            if (!dst[u]) continue;
+            if (wide[u]) st4(dst[u], v[u]);
+            else *dst[u] = v[u].x;
+        }
+    }
+}
+
 __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_kernel(float *tree, float *maxp, int cap, int levels,
                                                                         int capacity, const int32_t *idx_in,
                                                                         const float *prio, int batch,
@@ -1436,68 +1500,244 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_kernel(float *t
         }
         return;
     }
-    // gather: (draw, item) over the workgroup, items = state, next_state (float4
-    // where the rows are 16-byte aligned), action, reward, not_done; GU items
-    // per thread loaded before any is stored (the stores may alias the loads as
-    // far as the compiler knows: item by item, every load would wait for the
-    // previous store -- r04 first cut, 54 us per launch)
-    const int sd = st.state_dim, ad = st.action_dim;
-    const bool v4 = (sd & 3) == 0 && ((reinterpret_cast<uintptr_t>(st.state) | reinterpret_cast<uintptr_t>(st.next_state) |
-                                       reinterpret_cast<uintptr_t>(o_state) | reinterpret_cast<uintptr_t>(o_next)) & 15) == 0;
-    const int sv = v4 ? sd / 4 : sd, per = 2 * sv + ad + 2;
-    const int items = min(batch, UPD_THREADS) * per;
-    constexpr int GU = 8;
-    for (int it0 = threadIdx.x; it0 < items; it0 += GU * UPD_THREADS) {
-        float4 v[GU];
-        float *dst[GU];
-        bool wide[GU];
-#pragma unroll
-        for (int u = 0; u < GU; ++u) {
-            const int it = it0 + u * UPD_THREADS;
-            dst[u] = nullptr;
-            wide[u] = false;
-            if (it >= items) continue;
-            const int b = it / per, c = it - b * per;
-            const long d = (long)s * batch + b;
-            const long row = (long)s * (capacity + 1) + pick[b];
-            if (c < 2 * sv) {
-                const bool nx = c >= sv;
-                const int e = nx ? c - sv : c;
-                const float *src = (nx ? st.next_state : st.state) + row * sd;
-                float *o = (nx ? o_next : o_state) + d * sd;
-                if (v4) {
-                    v[u] = ld4(src + 4 * e);
-                    dst[u] = o + 4 * e;
-                    wide[u] = true;
-                } else {
-                    v[u].x = src[e];
-                    dst[u] = o + e;
-                }
-            } else if (c < 2 * sv + ad) {
-                const int e = c - 2 * sv;
-                v[u].x = st.action[row * ad + e];
-                dst[u] = o_action + d * ad + e;
-            } else if (c == 2 * sv + ad) {
-                v[u].x = st.reward[row];
-                dst[u] = o_reward + d;
-            } else {
-                v[u].x = st.not_done[row];
-                dst[u] = o_not_done + d;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < GU; ++u) {
-            if (!dst[u]) continue;
-            if (wide[u]) st4(dst[u], v[u]);
-            else *dst[u] = v[u].x;
-        }
-    }
+    gather_picked(st, capacity, s, batch, pick, o_state, o_action, o_next, o_reward, o_not_done);
     __syncthreads();
     if (threadIdx.x == 0) {  // `call` was read (and used) before this add: no fence needed
         if (atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
             *rng.counter = call + 1ull;
             *rng.ticket = 0u;
         }
+    }
+}
+
+// lap_update_sample_kernel with its dependent global-memory round trips
+// collapsed (batch <= CHAIN_MAXB; EXO_LAP_CHAIN=0 or a larger batch: the kernel
+// above).  That kernel waits for memory about 20 times in a row at the
+// bench's shape (cap 2^18, G = 6 levels below the staged top): the counter
+// and indices, the priorities, two trips for each global level (the index
+// re-read, then the children; every level's barrier also waits for the
+// level's stores), the staging, the sizes, the prefix walk, two for the
+// descent and the ticket; the 12 LDS levels re-read their index from global
+// memory as well.  Here, from the start to the idx_out store, a thread waits
+// for memory 4 times, and once more for the ticket -- 5 dependent trips:
+//   1. everything that depends on nothing, in one batch: the call counter,
+//      size[s], the draw's index (kept in a register from here on), its
+//      priority (or |td| pair) and the staged top of the tree (8 loads);
+//   2. the siblings of the draw's G global ancestors (lap_chain.h) and the
+//      prefix walk's G addends below the staged top (the siblings of leaf
+//      size[s]'s ancestors: thread `batch` loads them as if leaf size[s]
+//      were its draw), as soon as the index and the size are there.
+//      While they fly the workgroup finds the superseded duplicates and the
+//      chain partners in LDS.  The G levels are then G LDS-only barriers; the
+//      sums also go to the tree, stores nothing waits for.  A prefix addend
+//      this update changes is taken from the chain (leaf size[s] is one more
+//      row of the partner table), and the level-G values patch the staged
+//      top: both were loaded before this launch changed them;
+//   3., 4. the descent below the staged top, three levels per trip, after a
+//      barrier that finds the chain's stores long complete;
+//   5. the tail: the ticket's atomic, after the idx_out store.
+// What the phase stamps showed (profiles/lap_chain/README.md): neither kernel
+// is a pure latency chain.  Trip 2 is bound by the CU's rate of missed lines
+// (batch x G scattered 64-byte lines, about 6 cycles each), and the rest by
+// the instructions the two waves that hold the draws execute once each -- so
+// work those waves need not do is kept off them: the partner scan is spread
+// over the workgroup four slots per LDS read, the uniforms are drawn by waves
+// of other SIMDs, the batch maximum is reduced by the last wave.
+// The same operands in the same order as lap_update_kernel's level sweeps and
+// lap_sample_gather_kernel's walks: every node, index and row bit-identical
+// (tests/test_lap_chain_host.py, tests/test_lap_update_sample_chain_gpu.py).
+// idx_in may be idx_out (the caller's previous batch in the same slot): the
+// index is read once, at the start, by the thread that later writes it.
+constexpr int CHAIN_MAXB = 256;  // batch bound: LDS, and 1,024 threads give each table row >= 2 scanning threads
+constexpr int CHAIN_MAXG = 12;   // global levels (cap 2^24 under an 8,192-node top)
+constexpr int CHAIN_ROW = CHAIN_MAXB + 1;  // the draws and leaf size[s]
+constexpr int CHAIN_TOPLV = 12;            // at most this many levels in the staged top
+static_assert((2 << CHAIN_TOPLV) >= TOPN_US, "CHAIN_TOPLV: the staged top's levels");
+constexpr int CHAIN_PAD = 0x40000000;      // li[] padding: no slot's duplicate or partner (slots are < 2^24)
+constexpr int CHAIN_RNG0 = 640;            // the threads that draw the uniforms (waves on other SIMDs than the draws')
+
+// A workgroup barrier for LDS traffic alone: __syncthreads() would also wait
+// for the wave's global stores and, with them, for every load in flight.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_chain_kernel(
+    float *tree, float *maxp, int cap, int levels, int capacity, const int32_t *idx_in,
+    const float *__restrict__ prio, int batch, const int32_t *__restrict__ size, lap_storage_desc st, SampleRng rng,
+    int32_t *idx_out, float *o_state, float *o_action, float *o_next, float *o_reward, float *o_not_done, TdPrio tp,
+    bool gather) {
+    const int s = blockIdx.x, t = threadIdx.x;
+    float *T = stratum_tree(tree, s, cap);
+    __shared__ float red[UPD_THREADS / 64];
+    __shared__ __attribute__((aligned(16))) int32_t li[CHAIN_MAXB + 4];  // the draws' slots, padded to a multiple of 4
+    __shared__ int32_t lsz;                              // leaf size[s], row `batch` of the partner table
+    __shared__ float uni[CHAIN_MAXB];                    // the draws' uniforms
+    __shared__ int32_t later[CHAIN_MAXB];                // a later duplicate of the draw's slot exists
+    __shared__ int32_t partner[CHAIN_MAXG * CHAIN_ROW];  // [lv][b]: the draw below b's level-lv sibling, or -1
+    __shared__ float chain[2][CHAIN_MAXB];
+    __shared__ float lowval[CHAIN_MAXG];                 // the prefix addends below the staged top, final
+    __shared__ float top[TOPN_US];
+    __shared__ int32_t pick[CHAIN_MAXB];
+    const int G = lap_chain::global_levels(levels, TOPN_US);
+    const int lim = min(TOPN_US, 2 * cap);
+    const bool draw = t < batch;
+    const long d = (long)s * batch + (draw ? t : 0);
+    // ---- trip 1: nothing here depends on a load (addresses clamped, not
+    // branched around: every load is issued before the first wait)
+    const unsigned long long call = *rng.counter;  // read before any workgroup can take the ticket
+    const int sz = size[s];
+    const int me = idx_in[d];
+    const float *pp = tp.td ? tp.td + 2 * d : prio + d;
+    const float p0 = pp[0], p1 = pp[tp.td ? 1 : 0];  // the priority, or the |td| pair
+    constexpr int PER = TOPN_US / UPD_THREADS;
+    float stage[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) stage[j] = T[min(t + j * UPD_THREADS, lim - 1)];
+    for (int i = t; i < G * CHAIN_ROW; i += UPD_THREADS) partner[i] = -1;
+    if (t < CHAIN_MAXB + 4) li[t] = draw ? me : CHAIN_PAD;
+    if (draw) later[t] = 0;
+    if (t >= CHAIN_RNG0 && t < CHAIN_RNG0 + batch) {  // draw t - CHAIN_RNG0's uniform, off the draws' waves
+        uint32_t r[4];
+        philox_block(rng.seed, rng.tag, call, (uint32_t)(s * batch + t - CHAIN_RNG0), r);
+        uni[t - CHAIN_RNG0] = u01_open_hi(r[0]);
+    }
+    const int szl = min(sz, cap - 1);  // the prefix walk's leaf (sz >= cap: the root is the total)
+    // thread `batch` stands for leaf sz: its siblings are the prefix walk's addends
+    const int leaf = t == batch ? szl : me;
+    if (t == batch) lsz = szl;
+    // ---- trip 2: the siblings of the leaf's global ancestors
+    float sib[CHAIN_MAXG];
+#pragma unroll
+    for (int lv = 0; lv < CHAIN_MAXG; ++lv) sib[lv] = 0.0f;
+    if (t <= batch) {
+#pragma unroll
+        for (int lv = 0; lv < CHAIN_MAXG; ++lv) sib[lv] = T[lap_chain::sibling_of(cap, leaf, min(lv, max(G - 1, 0)))];
+    }
+    lds_barrier();
+    {   // superseded duplicates and partners: table row b scanned by 2^lp threads, four slots per read;
+        // a slot is a duplicate (xor 0), a partner (xor below 2^G) or, nearly always, neither
+        int lp = 0;
+        while (((batch + 1) << (lp + 1)) <= UPD_THREADS) ++lp;
+        const int b = t >> lp, part = t & ((1 << lp) - 1);
+        const int chunk = (((batch + 3) >> 2) + (1 << lp) - 1) >> lp;  // reads of four slots per thread
+        if (b <= batch) {
+            const int mine = b < batch ? li[b] : lsz;
+            const unsigned near = 1u << G;
+            bool sup = false;
+            for (int q = part * chunk; q < (part + 1) * chunk && 4 * q < batch; ++q) {
+                const int4 o = *reinterpret_cast<const int4 *>(&li[4 * q]);
+                const int other[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int k = 4 * q + j;
+                    if ((unsigned)(mine ^ other[j]) >= near) continue;
+                    const int lv = lap_chain::partner_level(mine, other[j]);
+                    if (lv < 0) sup |= b < batch && lap_chain::superseded_by(b, mine, k, other[j]);
+                    else atomicMax(&partner[lv * CHAIN_ROW + b], k);
+                }
+            }
+            if (sup) later[b] = 1;
+        }
+    }
+    const float pb = !draw ? 0.0f : tp.td ? powf(fmaxf(fmaxf(p0, p1), tp.minp), tp.alpha) : p0;
+    float mx = pb;
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    if ((t & 63) == 0) red[t >> 6] = mx;
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+        const int i = t + j * UPD_THREADS;
+        if (i < lim) top[i] = stage[j];
+    }
+    lds_barrier();
+    const bool carry = draw && !later[t];  // the last duplicate of its slot: it writes the leaf and runs the chain
+    if (draw && tp.td && tp.out) tp.out[d] = pb;
+    float cur = pb;
+    if (carry) {
+        T[cap + me] = pb;
+        chain[0][t] = pb;
+    }
+    if (t == batch) {  // the prefix addends no draw changes: as loaded
+#pragma unroll
+        for (int lv = 0; lv < CHAIN_MAXG; ++lv)
+            if (lv < G && partner[lv * CHAIN_ROW + batch] < 0) lowval[lv] = sib[lv];
+    }
+#pragma unroll
+    for (int lv = 0; lv < CHAIN_MAXG; ++lv) {
+        if (lv < G) lds_barrier();
+        if (lv < G && carry) {
+            if (partner[lv * CHAIN_ROW + batch] == t) lowval[lv] = cur;
+            const int node = lap_chain::node_of(cap, me, lv), k = partner[lv * CHAIN_ROW + t];
+            cur = lap_chain::chain_step(node, cur, k >= 0 ? chain[lv & 1][k] : sib[lv]);
+            T[node >> 1] = cur;
+            chain[(lv + 1) & 1][t] = cur;
+        }
+    }
+    if (carry) top[lap_chain::node_of(cap, me, G)] = cur;  // the staged value was loaded before this update
+    for (int lv = G + 1; lv <= levels; ++lv) {
+        lds_barrier();
+        if (draw) {
+            const int node = lap_chain::node_of(cap, me, lv);
+            top[node] = top[2 * node] + top[2 * node + 1];
+        }
+    }
+    __syncthreads();  // the tree's global levels are final for every thread of the workgroup
+    const int wb = min(TOPN_US / 2, cap);
+    for (int i = 1 + t; i < wb; i += UPD_THREADS) T[i] = top[i];
+    if (t >= UPD_THREADS - 64) {  // the last wave (no draws there): the batch's largest priority
+        float m = red[t & (UPD_THREADS / 64 - 1)];
+        for (int o = UPD_THREADS / 128; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        // priorities are >= min_priority^alpha > 0: int order == float order
+        if (t == UPD_THREADS - 64) atomicMax(reinterpret_cast<int *>(maxp), __float_as_int(m));
+    }
+    // ---- the next batch of this stratum
+    if (draw) {
+        const int ltop = levels - G;  // the levels of the staged top
+        float tot;
+        if (sz >= cap) {
+            tot = top[1];
+        } else {  // prefix_sum's additions in its order: the staged steps (read together), then the global ones
+            float x[CHAIN_TOPLV];
+#pragma unroll
+            for (int j = 0; j < CHAIN_TOPLV; ++j) {
+                const int lv = levels - 1 - j;
+                x[j] = j < ltop ? top[2 * ((1 << j) | (sz >> (lv + 1)))] : 0.0f;
+            }
+            tot = 0.0f;
+#pragma unroll
+            for (int j = 0; j < CHAIN_TOPLV; ++j)
+                if (j < ltop) tot += ((sz >> (levels - 1 - j)) & 1) ? x[j] : 0.0f;
+#pragma unroll
+            for (int lv = CHAIN_MAXG - 1; lv >= 0; --lv) {
+                if (lv >= G) continue;
+                tot += ((sz >> lv) & 1) ? lowval[lv] : 0.0f;
+            }
+        }
+        float val = uni[t] * tot;
+        // the staged levels from LDS one at a time, then (trips 3, 4) the global ones, three per trip
+        int node = 1;
+        for (int lv = 0; lv < ltop; ++lv) {
+            const float left = top[2 * node], right = top[2 * node + 1];
+            if (val <= left || right <= 0.0f) {
+                node = 2 * node;
+            } else {
+                val -= left;
+                node = 2 * node + 1;
+            }
+        }
+        node = descend_from([T](int n) { return T[n]; }, val, node, ltop, levels);
+        int i = node - cap;
+        if (i >= sz) i = sz > 0 ? sz - 1 : 0;
+        idx_out[d] = i;
+        pick[t] = i;
+    }
+    __syncthreads();
+    if (gather) {
+        gather_picked(st, capacity, s, batch, pick, o_state, o_action, o_next, o_reward, o_not_done);
+        __syncthreads();
+    }
+    // ---- trip 5; `call` was read (and used) before this add: no fence needed
+    if (t == 0 && atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
+        *rng.counter = call + 1ull;
+        *rng.ticket = 0u;
     }
 }
 
@@ -1517,6 +1757,26 @@ bool gather_split() {
         return !(e && e[0] == '0');
     }();
     return on;
+}
+
+// lap_update_sample's launch: the sibling-chain kernel up to CHAIN_MAXB draws per
+// stratum (EXO_LAP_CHAIN=0: always lap_update_sample_kernel, the level sweeps;
+// read per call, the parity test switches it).  Both compute the same bits.
+void launch_update_sample(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *idx_in, const float *prio,
+                          int batch, SampleRng rng, int32_t *idx_out, float *o_state, float *o_action, float *o_next,
+                          float *o_reward, float *o_not_done, TdPrio tp, bool gather, void *stream) {
+    const char *e = getenv("EXO_LAP_CHAIN");
+    const int levels = levels_of(t);
+    const bool chain = !(e && e[0] == '0') && batch <= CHAIN_MAXB && levels >= 1 &&
+                       lap_chain::global_levels(levels, TOPN_US) <= CHAIN_MAXG;
+    if (chain)
+        hipLaunchKernelGGL(lap_update_sample_chain_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
+                           t->tree, t->max_priority, t->cap, levels, t->capacity, idx_in, prio, batch, st->size, *st,
+                           rng, idx_out, o_state, o_action, o_next, o_reward, o_not_done, tp, gather);
+    else
+        hipLaunchKernelGGL(lap_update_sample_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
+                           t->tree, t->max_priority, t->cap, levels, t->capacity, idx_in, prio, batch, st->size, *st,
+                           rng, idx_out, o_state, o_action, o_next, o_reward, o_not_done, tp, gather);
 }
 
 int gather_after(const lap_tree_desc *t, const lap_storage_desc *st, int batch, const int32_t *idx, float *o_state,
@@ -1727,10 +1987,9 @@ int lap_update_sample_rng(const lap_tree_desc *t, const lap_storage_desc *st, co
     if (!valid(t) || !st || !st->size || !idx_in || !prio || !counter || !ticket || !idx_out || batch <= 0 ||
         batch > UPD_THREADS || !out_state || !out_action || !out_next_state || !out_reward || !out_not_done)
         return EXO_EINVAL;
-    hipLaunchKernelGGL(lap_update_sample_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
-                       t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, idx_in, prio, batch, st->size,
-                       *st, SampleRng{seed, tag, counter, ticket}, idx_out, out_state, out_action, out_next_state,
-                       out_reward, out_not_done, TdPrio{nullptr, 0.f, 0.f, nullptr}, !gather_split());
+    launch_update_sample(t, st, idx_in, prio, batch, SampleRng{seed, tag, counter, ticket}, idx_out, out_state,
+                         out_action, out_next_state, out_reward, out_not_done, TdPrio{nullptr, 0.f, 0.f, nullptr},
+                         !gather_split(), stream);
     return gather_after(t, st, batch, idx_out, out_state, out_action, out_next_state, out_reward, out_not_done, stream);
 }
 
@@ -1740,10 +1999,8 @@ int lap_update_sample_idx(const lap_tree_desc *t, const lap_storage_desc *st, co
     if (!valid(t) || !st || !st->size || !idx_in || !prio || !counter || !ticket || !idx_out || batch <= 0 ||
         batch > UPD_THREADS)
         return EXO_EINVAL;
-    hipLaunchKernelGGL(lap_update_sample_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
-                       t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, idx_in, prio, batch, st->size,
-                       *st, SampleRng{seed, tag, counter, ticket}, idx_out, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, TdPrio{nullptr, 0.f, 0.f, nullptr}, false);
+    launch_update_sample(t, st, idx_in, prio, batch, SampleRng{seed, tag, counter, ticket}, idx_out, nullptr, nullptr,
+                         nullptr, nullptr, nullptr, TdPrio{nullptr, 0.f, 0.f, nullptr}, false, stream);
     return rc(hipGetLastError());
 }
 
@@ -1768,11 +2025,9 @@ int lap_update_sample_td(const lap_tree_desc *t, const lap_storage_desc *st, con
     if (!valid(t) || !st || !st->size || !idx_in || !td || !counter || !ticket || !idx_out || batch <= 0 ||
         batch > UPD_THREADS || !out_state || !out_action || !out_next_state || !out_reward || !out_not_done)
         return EXO_EINVAL;
-    hipLaunchKernelGGL(lap_update_sample_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
-                       t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, idx_in, (const float *)nullptr,
-                       batch, st->size, *st, SampleRng{seed, tag, counter, ticket}, idx_out, out_state, out_action,
-                       out_next_state, out_reward, out_not_done, TdPrio{td, alpha, min_priority, prio_out},
-                       !gather_split());
+    launch_update_sample(t, st, idx_in, nullptr, batch, SampleRng{seed, tag, counter, ticket}, idx_out, out_state,
+                         out_action, out_next_state, out_reward, out_not_done,
+                         TdPrio{td, alpha, min_priority, prio_out}, !gather_split(), stream);
     return gather_after(t, st, batch, idx_out, out_state, out_action, out_next_state, out_reward, out_not_done, stream);
 }
 
