@@ -50,29 +50,20 @@ import torch
 
 from helpers import (GOLDEN, TD7_FULL_LEARNING_STEPS, TD7_FULL_QBOUNDS, TD7_GOLDENS, td7_full_batch,
                      td7_full_sample_index)
-from exo_amd.td7 import Critic, Hyperparameters, TD7Learner
-
-TOL = {"fp32": dict(grad=1e-4, delta=1e-3, prio=1e-5, bound=1e-5, mask=0.02),
-       "bf16": dict(grad=1e-2, golden=3e-2, delta=0.15, prio=1e-3, bound=1e-3, mask=0.1),
-       "fp16": dict(grad=1e-2, golden=3e-2, delta=0.15, prio=1e-3, bound=1e-3, mask=0.1)}
-COND = 4.0  # bounds scale with the reference's own fp32 deviation from fp64 ("noise")
-# sqrt(u / eps32) with eps32 = 1e-7 (fp32-level perturbation): bf16 u = 2^-9, fp16 u = 2^-11
-AMP = {"fp32": 1.0, "bf16": (2.0 ** -9 / 1e-7) ** 0.5, "fp16": (2.0 ** -11 / 1e-7) ** 0.5}
-ROUND = {"fp32": None, "bf16": torch.bfloat16, "fp16": torch.float16}
-
+from td7_restate import (AMP, COND, NETS, ROUND, TOL, _copy_state, _cpu_learner, _f64_learner,  # noqa: F401
+                         _named, _rel, _RoundedGemm, _rounded_matmuls)
+from exo_amd.td7 import Hyperparameters, TD7Learner
 
 def _golden(name="td7_full"):
     return np.load(f"{GOLDEN}/{name}.npz", allow_pickle=False)
 
 
-def _cpu_learner(name="td7_full"):
-    hp = Hyperparameters(**TD7_GOLDENS[name][0])
-    torch.manual_seed(0)
-    return TD7Learner(80, 7, hp, learning_steps=TD7_FULL_LEARNING_STEPS, device="cpu", fused_adam=False)
+def _hp(golden="td7_full"):
+    return Hyperparameters(**TD7_GOLDENS[golden][0])
 
 
 def _learner(device, precision="fp32", golden="td7_full", fused_f32=False):
-    L = _cpu_learner(golden)
+    L = _cpu_learner(_hp(golden))
     if device == "cpu":
         L2 = L
     else:
@@ -92,30 +83,9 @@ def _learner(device, precision="fp32", golden="td7_full", fused_f32=False):
     return L2
 
 
-def _named(mod, mname, grad=False):
-    """Reference-named flat tensors of a module (the critic's stacked heads split)."""
-    out = {}
-    if isinstance(mod, Critic):
-        for k, names in enumerate(Critic.HEADS):
-            for what in ("weight", "bias"):
-                p = getattr(mod, f"{'w' if what == 'weight' else 'b'}{k}")
-                t = p.grad if grad else p
-                for h, n in enumerate(names):
-                    out[f"{mname}.{n}.{what}"] = None if t is None else t[h]
-        return out
-    for n, p in mod.named_parameters():
-        out[f"{mname}.{n}"] = p.grad if grad else p
-    return out
-
-
 def _sample(name, t):
     v = t.detach().float().cpu().numpy().reshape(-1)
     return v[td7_full_sample_index(name, v.size)], v
-
-
-def _rel(x, ref):
-    d = np.linalg.norm(ref.astype(np.float64))
-    return np.linalg.norm((x - ref).astype(np.float64)) / max(d, 1e-30)
 
 
 def _check_grads(g, step, L, mnames, precision, report, free, forced):
@@ -149,86 +119,7 @@ def _check_grads(g, step, L, mnames, precision, report, free, forced):
     return worst
 
 
-class _RoundedGemm(torch.autograd.Function):
-    """y = x @ w^T (+ b) with x, w rounded to `dt` (batched if 3-D); backward
-    with dY rounded for both GEMMs (fp16: after scaling by 2^10), the bias
-    gradient from the unrounded dY -- the reduced-precision td7_dense kernels'
-    arithmetic, in float64."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, dt):
-        r = lambda t: t.to(dt).to(t.dtype)  # noqa: E731
-        ctx.save_for_backward(x, w)
-        ctx.dt, ctx.has_b = dt, b is not None
-        y = r(x) @ r(w).transpose(-1, -2)
-        return y + b.unsqueeze(-2) if b is not None else y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        r = lambda t: t.to(ctx.dt).to(t.dtype)  # noqa: E731
-        gs = 1024.0 if ctx.dt == torch.float16 else 1.0  # fp16: dP scaled by 2^10 before rounding (grad_scale)
-        rdy = (dy * gs).to(ctx.dt).to(dy.dtype) / gs
-        dx = rdy @ r(w)
-        xx = x if x.dim() == dy.dim() else x.unsqueeze(0).expand(dy.shape[0], *x.shape)
-        dw = rdy.transpose(-1, -2) @ r(xx)
-        if dw.dim() > w.dim():
-            dw = dw.sum(0)
-        if dx.dim() > x.dim():
-            dx = dx.sum(0)
-        db = dy.sum(-2) if ctx.has_b else None
-        if db is not None and db.dim() > 1 and w.dim() == 2:
-            db = db.sum(0)
-        return dx, dw, db, None
-
-
-class _rounded_matmuls:
-    """Route the CPU path's F.linear / torch.baddbmm / torch.bmm through _RoundedGemm."""
-
-    def __init__(self, dt):
-        self.dt = dt
-
-    def __enter__(self):
-        import torch.nn.functional as F
-        self.saved = (F.linear, torch.baddbmm, torch.bmm)
-        dt = self.dt
-        F.linear = lambda x, w, b=None: _RoundedGemm.apply(x, w, b, dt)
-        torch.baddbmm = lambda b, x, wt: _RoundedGemm.apply(x, wt.transpose(1, 2), b.squeeze(1), dt)
-        torch.bmm = lambda x, wt: _RoundedGemm.apply(x, wt.transpose(1, 2), None, dt)
-
-    def __exit__(self, *a):
-        import torch.nn.functional as F
-        F.linear, torch.baddbmm, torch.bmm = self.saved
-
-
 _EXACT = {}
-NETS = ("actor", "critic", "encoder", "actor_target", "critic_target", "fixed_encoder", "fixed_encoder_target")
-
-
-def _f64_learner(golden):
-    """A float64 TD7Learner on the CPU (torch.optim.Adam, scalar state in fp64)."""
-    L = _cpu_learner(golden)
-    for name in NETS:
-        getattr(L, name).double()
-    L.actor_optimizer = torch.optim.Adam(L.actor.parameters(), lr=L.hp.actor_lr, weight_decay=1e-7)
-    L.critic_optimizer = torch.optim.Adam(L.critic.parameters(), lr=L.hp.critic_lr, weight_decay=1e-7)
-    L.encoder_optimizer = torch.optim.Adam(L.encoder.parameters(), lr=L.hp.encoder_lr, weight_decay=1e-7)
-    f64 = dict(dtype=torch.float64)
-    L.max, L.min = torch.tensor(-1e8, **f64), torch.tensor(1e8, **f64)
-    L.min_target, L.max_target = torch.tensor(TD7_FULL_QBOUNDS[0], **f64), torch.tensor(TD7_FULL_QBOUNDS[1], **f64)
-    L.target_policy_noise = L.target_policy_noise.double()
-    return L
-
-
-def _copy_state(dst, src):
-    """dst (fp64 CPU learner) <- src's weights and running scalars."""
-    with torch.no_grad():
-        for name in NETS:
-            for p, q in zip(getattr(dst, name).parameters(), getattr(src, name).parameters()):
-                p.copy_(q.detach().double().cpu())
-        for k in ("max", "min", "min_target", "max_target", "target_policy_noise"):
-            getattr(dst, k).copy_(getattr(src, k).detach().double().cpu())
-    dst.training_steps = src.training_steps
 
 
 def _grads(L, mnames, step):
@@ -246,7 +137,7 @@ def _free_run(golden):
     if golden in _EXACT:
         return _EXACT[golden]
     g = _golden(golden)
-    L = _f64_learner(golden)
+    L = _f64_learner(_hp(golden), TD7_FULL_QBOUNDS)
     out = {}
     for step in range(TD7_GOLDENS[golden][1]):
         s, a, s2, r, nd, nz = td7_full_batch(step)
@@ -268,7 +159,8 @@ def _run(device, precision="fp32", golden="td7_full", fused_f32=False):
     free = _free_run(golden)
     tol = TOL[precision]
     L = _learner(device, precision, golden, fused_f32)
-    X = _f64_learner(golden)  # teacher-forced restatement, reloaded from L before every phase
+    # the teacher-forced restatement, reloaded from L before every phase
+    X = _f64_learner(_hp(golden), TD7_FULL_QBOUNDS)
     rounding = _rounded_matmuls(ROUND[precision]) if ROUND[precision] is not None else None
     init = {}
     for mname in ("actor", "critic", "encoder"):
@@ -348,7 +240,7 @@ def _run(device, precision="fp32", golden="td7_full", fused_f32=False):
 def test_seeded_init_matches_reference_at_bench_shape(golden):
     """torch.manual_seed(0) initialisation at 300/320 (and 1,024) widths is bit-exact."""
     g = _golden(golden)
-    L = _cpu_learner(golden)
+    L = _cpu_learner(_hp(golden))
     for mname in ("actor", "critic", "encoder"):
         for name, t in _named(getattr(L, mname), mname).items():
             xs, full = _sample(name, t)
