@@ -43,10 +43,10 @@ __device__ __forceinline__ void stg(T *p, T v) {
     *(__attribute__((address_space(1))) T *)p = v;
 }
 
-constexpr int NW = 4;            // waves of one k-group: output tile t goes to wave t % NW
-constexpr int NKG = 2;           // k-groups: each gemm's k-steps are split over NKG sets of NW waves
+constexpr int NW = 4;            // waves of one group: output tile t goes to wave t % NW of a group
+constexpr int NKG = 2;           // wave groups: group kg owns its half of every wave's tile slots (see the GEMM core)
 constexpr int NTH = 64 * NW * NKG;  // threads per workgroup (2 waves per SIMD)
-constexpr int PD = TD7F_PD;    // k-steps of weight loads in flight per wave (k-steps are padded to multiples)
+constexpr int PD = TD7F_PD;    // packed k-steps are padded to multiples of it; the weight ring holds 2 PD k-steps
 constexpr int TR = 16;         // rows of one MFMA row tile
 
 enum Prec : int { PREC_BF16 = 1, PREC_F16 = 2, PREC_F32 = 3 };
@@ -144,182 +144,196 @@ struct Lin {
 // loads biases / saved activations as 16-byte vectors and writes 8-byte
 // (16-bit x 4) or 16-byte (fp32 x 4) LDS stores.
 //
-// Work split: output tile t (16 columns) of the NW * TH tiles from t0 goes to
-// wave t % NW of each k-group; the k-steps are split over the NKG = 2 k-groups
-// (multiples of PD each).  After the k-loop the groups exchange partial sums
-// through the LDS area at offset 0 so that group 0 finishes tiles i < (TH+1)/2
-// of each wave and group 1 the rest -- both halves of the workgroup run the
-// epilogue.
+// Work split: the NW * TH output tiles (16 columns each) from t0 are dealt to
+// the 8 waves whole: wave (w, kg) owns the tile slots i = j + kg h, j < OS
+// (h = (TH + 1) / 2: slots 0..h-1 for kg 0, h..TH-1 for kg 1 -- 3 and 2 tiles
+// at TH 5), tile t0 + w + NW i, and runs ALL k-steps for them: no partial sums
+// cross waves, so a GEMM needs no exchange and no barrier of its own.  The
+// sum keeps the order of the former two-k-group split bit for bit: one
+// accumulator chain over the k-steps [0, kA), a second one (from zero) over
+// [kA, ks), added once at the end (kchain_split).
 //
-// Weight stream: each wave keeps PD k-steps x TH tiles of 16-byte loads in
-// flight in a register ring that persists across layers: the tail of a GEMM
-// refills the ring with the first PD k-steps of the NEXT layer's weights, so
-// they load during this layer's epilogue and barrier.  Issue order is pinned
-// with scheduling barriers (loads in consumption order keep s_waitcnt at
-// vmcnt(20..24)).  The X fragment is read from LDS one k-step ahead.
+// Weight stream: each wave keeps RD = 2 PD k-steps x its owned tiles of 16-byte
+// loads in flight in a register ring that persists across layers (slot p holds
+// k-step p of a layer's first RD): a whole ks = 10 layer.  After the MFMAs of
+// a slot the slot is refilled with k-step + RD of the same layer or, in the
+// last round, with k-step p of the NEXT layer, so those load during this
+// layer's epilogue and barrier.  Issue order is pinned with scheduling
+// barriers, loads in consumption order (the compiler still merges a layer's
+// ring waits into one vmcnt(0) before its first MFMA: DESIGN.md section 4).  The
+// ring slot of a tile slot a wave does not own (kg 1's third at TH 5) is never
+// loaded (a wave-uniform guard, no dummy traffic) and stays zero.  The X
+// fragment is read from LDS one k-step ahead.
 struct GDesc {
     const u32x4 *wp;  // packed operand (forward wf or dX wb)
     int ks;           // k-steps (multiple of PD)
     int t0;           // first output tile
 };
 
-__device__ __forceinline__ void kgroup_range(int ks, int kg, int &kb, int &ke) {
-    const int kA = ks >= 2 * PD ? ((ks / 2 + PD - 1) / PD) * PD : ks;
-    kb = kg ? kA : 0;
-    ke = kg ? ks : kA;
+constexpr int RD = 2 * PD;                             // ring depth in k-steps
+constexpr int os_of(int th) { return (th + 1) / 2; }  // owned tile slots of a wave (kg 1: th - os_of(th))
+template <int TH>
+using Ring = u32x4[RD][os_of(TH)];
+
+// the wave's index as a scalar (threadIdx.x >> 6 is uniform, the compiler cannot know)
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+// tile slot of owned slot j of this wave (>= TH: the wave owns no such slot)
+template <int TH>
+__device__ __forceinline__ int own_slot(int j) {
+    return j + (wave_id() / NW) * os_of(TH);
 }
 
+// first k-step of the second accumulator chain (ks: none, the chain stays +0)
+__device__ __forceinline__ int kchain_split(int ks) { return ks >= 2 * PD ? ((ks / 2 + PD - 1) / PD) * PD : ks; }
+
+// the first min(ks, RD) k-steps of g into the ring
 template <int TH>
-__device__ __forceinline__ void ring_fill(u32x4 (&R)[PD][TH], const GDesc &g) {
-    const int wv = threadIdx.x >> 6, w = wv % NW, kg = wv / NW, lane = threadIdx.x & 63;
-    int kb, ke;
-    kgroup_range(g.ks, kg, kb, ke);
-    // a k-group with no k-steps of g reloads the first fragment instead of
-    // skipping: the loads stay unconditional, so s_waitcnt counts stay exact for
-    // the loads issued before the ring (kernel-start staging)
-    const bool live = ke > kb;
+__device__ __forceinline__ void ring_fill(Ring<TH> &R, const GDesc &g) {
+    constexpr int OS = os_of(TH);
+    const int w = wave_id() % NW, lane = threadIdx.x & 63;
 #pragma unroll
-    for (int p = 0; p < PD; ++p)
+    for (int p = 0; p < RD; ++p)
 #pragma unroll
-        for (int i = 0; i < TH; ++i) {
-            R[p][i] = ldg(g.wp + (live ? ((size_t)(g.t0 + w + NW * i) * g.ks + kb + p) * 64 : 0) + lane);
+        for (int j = 0; j < OS; ++j) {
+            const int i = own_slot<TH>(j);
+            R[p][j] = u32x4{0u, 0u, 0u, 0u};
+            if (i < TH && (p < PD || g.ks >= RD)) R[p][j] = ldg(g.wp + ((size_t)(g.t0 + w + NW * i) * g.ks + p) * 64 + lane);
             __builtin_amdgcn_sched_barrier(0);
         }
 }
 
-// acc[r][i] (tile t0 + w + NW i) over the rows 16r..16r+15 of the image at a_off.
-// Every thread of the workgroup calls it (one barrier).  The ring must hold g's
-// first PD k-steps (ring_fill or the previous gemm's `next`).
 // Epilogue operands loaded BEFORE the k-loop (vmcnt is in issue order: loaded
 // after the tail's prefetch of the next layer, they would wait for all of it):
-// ep[r][i] = vector at (col of slot i) of the bias (per column, r ignored) or of
-// a saved fp32 activation y[(row0 + row) * yld + col - c0] (per row).
+// ep[r][j] = vector at (col of owned slot j) of the bias (per column, r ignored)
+// or of a saved fp32 activation y[(row0 + row) * yld + col - c0] (per row).
 struct EpiSrc {
     const float *p;  // null: none
     long ld;         // 0: a bias row (same for every row); else row stride
     int c0, row0, nrows, ncols;
 };
 template <int RT, int TH>
-__device__ __forceinline__ void epi_prefetch(const EpiSrc &e, int t0, floatx4 (&ep)[RT][TH]) {
+__device__ __forceinline__ void epi_prefetch(const EpiSrc &e, int t0, floatx4 (&ep)[RT][os_of(TH)]) {
 #pragma unroll
-    for (int i = 0; i < TH; ++i) {
-        const int wv = threadIdx.x >> 6;
-        const int col = 16 * (t0 + wv % NW + NW * i) + 4 * ((threadIdx.x & 63) >> 4) - e.c0;
-        const bool mine = (i < (TH + 1) / 2) == (wv < NW);
+    for (int j = 0; j < os_of(TH); ++j) {
+        const int i = own_slot<TH>(j);
+        const int col = 16 * (t0 + wave_id() % NW + NW * i) + 4 * ((threadIdx.x & 63) >> 4) - e.c0;
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
             const int row = (threadIdx.x & 15) + TR * r;
-            const bool ok = e.p && mine && col >= 0 && col < e.ncols && (e.ld == 0 || e.row0 + row < e.nrows);
-            ep[r][i] = ok ? ldg((const floatx4 *)(e.p + (e.ld ? (long)(e.row0 + row) * e.ld : 0) + col))
+            const bool ok = e.p && i < TH && col >= 0 && col < e.ncols && (e.ld == 0 || e.row0 + row < e.nrows);
+            ep[r][j] = ok ? ldg((const floatx4 *)(e.p + (e.ld ? (long)(e.row0 + row) * e.ld : 0) + col))
                           : floatx4{0.f, 0.f, 0.f, 0.f};
         }
     }
 }
 
+// one k-step: the MFMAs of ring slot p on the X fragment of k-step s (an), the
+// fragment of k-step s + 1 (clamped to the last) read ahead
 template <int P, int RT, int TH>
-__device__ __forceinline__ void gemm(char *lds, int a_off, int lda, const GDesc &g, u32x4 (&R)[PD][TH],
-                                     floatx4 (&acc)[RT][TH], const GDesc *next, const EpiSrc &es,
-                                     floatx4 (&ep)[RT][TH]) {
-    const int wv = threadIdx.x >> 6, w = wv % NW, kg = wv / NW, lane = threadIdx.x & 63;
-    int kb, ke, nb = 0, ne = 0;
-    kgroup_range(g.ks, kg, kb, ke);
-    if (next) kgroup_range(next->ks, kg, nb, ne);
-    epi_prefetch(es, g.t0, ep);
+__device__ __forceinline__ void kstep(Ring<TH> &R, int p, const char *ap, int lda, int s, int n, u32x4 (&an)[RT],
+                                      floatx4 (&acc)[RT][os_of(TH)]) {
+    u32x4 x[RT];
+    const int sn = s + 1 < n ? s + 1 : n - 1;
 #pragma unroll
-    for (int r = 0; r < RT; ++r)
-#pragma unroll
-        for (int i = 0; i < TH; ++i) acc[r][i] = floatx4{0.f, 0.f, 0.f, 0.f};
-    if (ke > kb) {
-        const u32x4 *bp[TH];
-#pragma unroll
-        for (int i = 0; i < TH; ++i) bp[i] = g.wp + ((size_t)(g.t0 + w + NW * i) * g.ks + kb) * 64 + lane;
-        const char *ap = lds + a_off + ((lane & 15) * lda + 8 * (lane >> 4) + 32 * kb) * 2;
-        const int n = ke - kb;
-        u32x4 an[RT];
-#pragma unroll
-        for (int r = 0; r < RT; ++r) an[r] = *(const u32x4 *)(ap + r * TR * lda * 2);
-        int s0 = 0;
-        for (; s0 + PD < n; s0 += PD) {
-#pragma unroll
-            for (int p = 0; p < PD; ++p) {
-                const int s = s0 + p;
-                u32x4 x[RT];
-#pragma unroll
-                for (int r = 0; r < RT; ++r) {
-                    x[r] = an[r];
-                    an[r] = *(const u32x4 *)(ap + (r * TR * lda + 32 * (s + 1)) * 2);
-                }
-#pragma unroll
-                for (int j = 0; j < Ty<P>::SUB; ++j)
-#pragma unroll
-                    for (int i = 0; i < TH; ++i) {
-#pragma unroll
-                        for (int r = 0; r < RT; ++r) acc[r][i] = Ty<P>::mfma(R[p][i], x[r], acc[r][i], j);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-#pragma unroll
-                for (int i = 0; i < TH; ++i) {
-                    R[p][i] = ldg(bp[i] + (s + PD) * 64);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-        const u32x4 *np[TH];
-        if (ne > nb)
-#pragma unroll
-            for (int i = 0; i < TH; ++i) np[i] = next->wp + ((size_t)(next->t0 + w + NW * i) * next->ks + nb) * 64 + lane;
-#pragma unroll
-        for (int p = 0; p < PD; ++p) {
-            const int s = s0 + p;
-            u32x4 x[RT];
-#pragma unroll
-            for (int r = 0; r < RT; ++r) {
-                x[r] = an[r];
-                if (p + 1 < PD) an[r] = *(const u32x4 *)(ap + (r * TR * lda + 32 * (s + 1)) * 2);
-            }
-#pragma unroll
-            for (int j = 0; j < Ty<P>::SUB; ++j)
-#pragma unroll
-                for (int i = 0; i < TH; ++i) {
-#pragma unroll
-                    for (int r = 0; r < RT; ++r) acc[r][i] = Ty<P>::mfma(R[p][i], x[r], acc[r][i], j);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            if (ne > nb) {
-#pragma unroll
-                for (int i = 0; i < TH; ++i) {
-                    R[p][i] = ldg(np[i] + p * 64);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-    } else if (next) {
-        ring_fill(R, *next);
+    for (int r = 0; r < RT; ++r) {
+        x[r] = an[r];
+        an[r] = *(const u32x4 *)(ap + (r * TR * lda + 32 * sn) * 2);
     }
-    // exchange: group 0 keeps tiles i < h, group 1 tiles i >= h
-    constexpr int h = (TH + 1) / 2;
-    floatx4 *red = (floatx4 *)lds + ((w * 64 + lane) * RT) * TH;
+#pragma unroll
+    for (int j = 0; j < Ty<P>::SUB; ++j)
+#pragma unroll
+        for (int i = 0; i < os_of(TH); ++i) {
+#pragma unroll
+            for (int r = 0; r < RT; ++r) acc[r][i] = Ty<P>::mfma(R[p][i], x[r], acc[r][i], j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+}
+
+// acc[r][j] (owned slot j: tile t0 + w + NW own_slot(j)) over the rows
+// 16r..16r+15 of the image at a_off.  Every thread of the workgroup calls it.
+// The ring must hold g's first min(ks, RD) k-steps (ring_fill or the previous
+// gemm's `next`).  sync: one workgroup barrier between the k-loop and the
+// return, for the callers whose epilogue writes into the image the other
+// waves' k-loops still read (kernel-uniform).
+template <int P, int RT, int TH>
+__device__ __forceinline__ void gemm(char *lds, int a_off, int lda, const GDesc &g, Ring<TH> &R,
+                                     floatx4 (&acc)[RT][os_of(TH)], const GDesc *next, const EpiSrc &es,
+                                     floatx4 (&ep)[RT][os_of(TH)], bool sync) {
+    constexpr int OS = os_of(TH);
+    const int w = wave_id() % NW, lane = threadIdx.x & 63;
+    const int n = g.ks, kA = kchain_split(n), nk = next ? next->ks : 0;
+    epi_prefetch<RT, TH>(es, g.t0, ep);
+    floatx4 first[RT][OS];  // the chain over [0, kA) once the second one runs
 #pragma unroll
     for (int r = 0; r < RT; ++r)
 #pragma unroll
-        for (int i = 0; i < TH; ++i)
-            if ((i < h) != (kg == 0)) red[r * TH + i] = acc[r][i];
-    __syncthreads();
+        for (int j = 0; j < OS; ++j) acc[r][j] = first[r][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+    bool own[OS];
+    const u32x4 *bp[OS], *np[OS];
+#pragma unroll
+    for (int j = 0; j < OS; ++j) {
+        const int i = own_slot<TH>(j);
+        own[j] = i < TH;
+        const int t = w + NW * (own[j] ? i : 0);  // (an unowned slot's pointers are never used)
+        bp[j] = g.wp + (size_t)(g.t0 + t) * n * 64 + lane;
+        np[j] = next ? next->wp + (size_t)(next->t0 + t) * nk * 64 + lane : bp[j];
+    }
+    const char *ap = lds + a_off + ((lane & 15) * lda + 8 * (lane >> 4)) * 2;
+    u32x4 an[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) an[r] = *(const u32x4 *)(ap + r * TR * lda * 2);
+    int s0 = 0;
+    // whole rounds of the ring with more of this layer behind them
+    for (; n - s0 > RD; s0 += RD) {
+        const bool more = n - s0 >= 2 * RD;  // the k-steps s0 + RD + PD.. exist
+#pragma unroll
+        for (int p = 0; p < RD; ++p) {
+            if (p % PD == 0 && s0 + p == kA) {
+#pragma unroll
+                for (int r = 0; r < RT; ++r)
+#pragma unroll
+                    for (int j = 0; j < OS; ++j) first[r][j] = acc[r][j], acc[r][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+            }
+            kstep<P, RT, TH>(R, p, ap, lda, s0 + p, n, an, acc);
+            if (p < PD || more) {
+#pragma unroll
+                for (int j = 0; j < OS; ++j) {
+                    if (own[j]) R[p][j] = ldg(bp[j] + (size_t)(s0 + p + RD) * 64);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    }
+    // the last round (PD or RD k-steps): every slot is refilled with the next layer's
+    const bool full = n - s0 == RD;
+#pragma unroll
+    for (int p = 0; p < RD; ++p) {
+        if (p < PD || full) {
+            if (p % PD == 0 && s0 + p == kA && kA < n) {
+#pragma unroll
+                for (int r = 0; r < RT; ++r)
+#pragma unroll
+                    for (int j = 0; j < OS; ++j) first[r][j] = acc[r][j], acc[r][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+            }
+            kstep<P, RT, TH>(R, p, ap, lda, s0 + p, n, an, acc);
+        }
+        if (next && (p < PD || nk >= RD)) {
+#pragma unroll
+            for (int j = 0; j < OS; ++j) {
+                if (own[j]) R[p][j] = ldg(np[j] + p * 64);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    }
+    if (sync) __syncthreads();
 #pragma unroll
     for (int r = 0; r < RT; ++r)
 #pragma unroll
-        for (int i = 0; i < TH; ++i)
-            if ((i < h) == (kg == 0)) acc[r][i] += red[r * TH + i];
+        for (int j = 0; j < OS; ++j) acc[r][j] += first[r][j];
 }
 
-// bytes of the LDS exchange area gemm uses (offset 0 of every fused kernel)
-constexpr int red_bytes(int rt, int tpw) { return NW * 64 * rt * tpw * 16; }
-
-// This wave finishes tile slot i (see gemm); its columns and row.
-template <int TH>
-__device__ __forceinline__ bool owns(int i) {
-    return (i < (TH + 1) / 2) == ((threadIdx.x >> 6) < NW);
-}
+// The columns (first of the lane's 4) of tile slot i = own_slot<TH>(j) of this
+// wave, and the lane's row.
 __device__ __forceinline__ int acc_col(int t0, int i) {
     const int wv = threadIdx.x >> 6;
     return 16 * (t0 + wv % NW + NW * i) + 4 * ((threadIdx.x & 63) >> 4);
@@ -362,13 +376,14 @@ __device__ __forceinline__ void put4(char *lds, R16 r, int row, int col, const f
 // owned columns n < N, written to any of: 16-bit LDS image (column col0 + n),
 // fp32 LDS region, global fp32 [row0+row][n] (rows < nrows).
 template <int P, int RT, int TH>
-__device__ __forceinline__ void epi_fwd(char *lds, const floatx4 (&acc)[RT][TH], const floatx4 (&bias)[RT][TH], int N,
-                                        int act, R16 o16, int col0, R32 o32, float *g, long gld, int row0,
-                                        int nrows) {
+__device__ __forceinline__ void epi_fwd(char *lds, const floatx4 (&acc)[RT][os_of(TH)],
+                                        const floatx4 (&bias)[RT][os_of(TH)], int N, int act, R16 o16, int col0,
+                                        R32 o32, float *g, long gld, int row0, int nrows) {
 #pragma unroll
-    for (int i = 0; i < TH; ++i) {
-        if (!owns<TH>(i)) continue;
-        const int n = acc_col(0, i);
+    for (int i = 0; i < os_of(TH); ++i) {
+        const int slot = own_slot<TH>(i);
+        if (slot >= TH) continue;
+        const int n = acc_col(0, slot);
         if (n >= N) continue;
         const floatx4 b = bias[0][i];
 #pragma unroll
@@ -392,13 +407,14 @@ __device__ __forceinline__ void epi_fwd(char *lds, const floatx4 (&acc)[RT][TH],
 // gradient operand dP: the 16-bit LDS image (x gs) and the fp32 column sums of
 // the rows (bias-gradient partials part[m], written by lanes 0..3 of a column group).
 template <int P, int RT, int TH>
-__device__ __forceinline__ void epi_bwd(char *lds, const floatx4 (&acc)[RT][TH], int t0, int c0, int c1, int act,
-                                        const floatx4 (&yv_)[RT][TH], R32 o32, float *g, long gld, R16 o16,
-                                        float *part, int row0, int nrows) {
+__device__ __forceinline__ void epi_bwd(char *lds, const floatx4 (&acc)[RT][os_of(TH)], int t0, int c0, int c1,
+                                        int act, const floatx4 (&yv_)[RT][os_of(TH)], R32 o32, float *g, long gld,
+                                        R16 o16, float *part, int row0, int nrows) {
 #pragma unroll
-    for (int i = 0; i < TH; ++i) {
-        if (!owns<TH>(i)) continue;
-        const int col = acc_col(t0, i);
+    for (int i = 0; i < os_of(TH); ++i) {
+        const int slot = own_slot<TH>(i);
+        if (slot >= TH) continue;
+        const int col = acc_col(t0, slot);
         const bool in = col >= c0 && col < c1;
         const int m = col - c0;
         float cs[4] = {0.f, 0.f, 0.f, 0.f};
@@ -519,8 +535,10 @@ struct RowStage {
 };
 __device__ __forceinline__ void row_issue(RowStage &s, const float *src, long sld, int ncols, int row0, int nrows) {
     const int c = min((int)threadIdx.x, ncols - 1);
+    // (clamped to the last row, not to row0: the second 16-row tile of a
+    // 32-row select workgroup may start past nrows)
 #pragma unroll
-    for (int r = 0; r < TR; ++r) s.v[r] = ldg(src + (long)(row0 + r < nrows ? row0 + r : row0) * sld + c);
+    for (int r = 0; r < TR; ++r) s.v[r] = ldg(src + (long)min(row0 + r, nrows - 1) * sld + c);
 }
 __device__ __forceinline__ void row_add(RowStage &s, const RowStage &o) {
 #pragma unroll
@@ -776,24 +794,38 @@ static __device__ unsigned long long *g_td7f_stamps;  // per translation unit
 
 // ---------------------------------------------------------------- layers
 
+// A layer's epilogue runs while other waves may still be in the k-loop, reading
+// the source image `a` (rows x a.ld 16-bit units): it needs the gemm's barrier
+// exactly when one of its LDS destinations intersects that image (the overlaid
+// layouts: F over H1 | H2, the fp32 passes' dP / dY images).  Kernel-uniform.
+// Everything else a layer may race with is ordered by the closing barrier of
+// the layer before it (barrier audit).
+__device__ __forceinline__ bool epi_aliases(R16 a, int rows, R16 o16, R32 o32) {
+    const int a0 = a.off, a1 = a.off + rows * a.ld * 2;
+    const bool h16 = o16.off >= 0 && o16.off < a1 && a0 < o16.off + rows * o16.ld * 2;
+    const bool h32 = o32.off >= 0 && o32.off < a1 && a0 < o32.off + rows * o32.ld * 4;
+    return h16 || h32;
+}
+
 // One forward MFMA Linear: gemm over the image `a` (the ring holds its first
 // k-steps) + epilogue; `next` = the next MFMA layer of the pass (its weights
 // start loading in this layer's tail).  Ends with a barrier.
 template <int P, int RT, int TH>
-__device__ __forceinline__ void layer_fwd(char *lds, u32x4 (&R)[PD][TH], R16 a, const Lin &L, const GDesc *next,
+__device__ __forceinline__ void layer_fwd(char *lds, Ring<TH> &R, R16 a, const Lin &L, const GDesc *next,
                                           int act, R16 o16, int col0, R32 o32, float *g, long gld, int row0,
                                           int nrows, int &si) {
     FSTAMP(si);
-    floatx4 acc[RT][TH], bias[RT][TH];
+    floatx4 acc[RT][os_of(TH)], bias[RT][os_of(TH)];
     const GDesc gd{L.wf, L.ksf, 0};
-    gemm<P, RT, TH>(lds, a.off, a.ld, gd, R, acc, next, EpiSrc{L.b, 0, 0, 0, 0, L.N}, bias);
+    gemm<P, RT, TH>(lds, a.off, a.ld, gd, R, acc, next, EpiSrc{L.b, 0, 0, 0, 0, L.N}, bias,
+                    epi_aliases(a, RT * TR, o16, o32));
     FSTAMP(si);
     epi_fwd<P, RT, TH>(lds, acc, bias, L.N, act, o16, col0, o32, g, gld, row0, nrows);
     __syncthreads();
 }
 // ... with the next layer's forward operand as `next`
 template <int P, int RT, int TH>
-__device__ __forceinline__ void layer_fwd(char *lds, u32x4 (&R)[PD][TH], R16 a, const Lin &L, const Lin *next, int act,
+__device__ __forceinline__ void layer_fwd(char *lds, Ring<TH> &R, R16 a, const Lin &L, const Lin *next, int act,
                                           R16 o16, int col0, R32 o32, float *g, long gld, int row0, int nrows,
                                           int &si) {
     GDesc gn{nullptr, 0, 0};
@@ -877,8 +909,7 @@ inline int ks_of(int k, int kd = 32) { return round_up((k + kd - 1) / kd, PD); }
 inline int ld16(int n, int kd = 32) { return ks_of(n, kd) * 32 + 16; }
 
 struct Bump {
-    int off;
-    explicit Bump(int rt) : off(red_bytes(rt, 5)) {}  // gemm's reduction area at offset 0
+    int off = 0;
     R16 r16(int rows, int ld) {
         R16 r{off, ld};
         off += round_up(rows * ld * 2, 16);

@@ -318,8 +318,8 @@ struct SelectArgs {
 };
 
 #define RING_START(first)      \
-    u32x4 R[PD][TH];           \
-    ring_fill(R, GDesc{(first).wf, (first).ksf, 0})
+    Ring<TH> R;                \
+    ring_fill<TH>(R, GDesc{(first).wf, (first).ksf, 0})
 
 __device__ __forceinline__ R16 rows_of(R16 r, int t) { return R16{r.off + t * TR * r.ld * 2, r.ld}; }
 __device__ __forceinline__ R32 rows_of(R32 r, int t) { return R32{r.off + t * TR * r.ld * 4, r.ld}; }
@@ -405,8 +405,12 @@ __global__ __launch_bounds__(NTH) void select_kernel(SelectArgs a) {
     __syncthreads();
     // F overlaid H1 | H2: their zero padding columns (read by the GEMMs below
     // where the width is not a multiple of 32 PD) are restored before the
-    // epilogues write H1 / H2 (those come after each GEMM's exchange barrier)
-    if (a.F.off == a.H1.off) zero_lds(lds + a.H1.off, a.H2.off + rows * a.H2.ld * 2 - a.H1.off);
+    // epilogues write H1 / H2 (a fast wave's epilogue may start while another
+    // wave still zeroes: the barrier orders them)
+    if (a.F.off == a.H1.off) {
+        zero_lds(lds + a.H1.off, a.H2.off + rows * a.H2.ld * 2 - a.H1.off);
+        __syncthreads();
+    }
     layer_fwd<P, RT, TH>(lds, R, a.CAT, a.ac[1], &a.ac[2], a.act_actor, a.H1, 0, NO32, nullptr, 0, row0, a.n, si);
     layer_fwd<P, RT, TH>(lds, R, a.H1, a.ac[2], (const Lin *)nullptr, a.act_actor, a.H2, 0, NO32, nullptr, 0, row0, a.n, si);
     if constexpr (RT == 1) {
@@ -758,7 +762,7 @@ int select_impl(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
                    : rt_env && (rt_env[0] == '1' || rt_env[0] == '2') ? rt_env[0] - '0'
                    : rt ? rt : (n > 8192 ? 2 : 1);
     const int rows = RT * TR, hmax = std::max(enc[0].n_out, std::max(enc[1].n_out, std::max(a.Ha, actor[1].n_out)));
-    Bump b(RT);
+    Bump b;
     a.X = b.r16(rows, ld16(a.S, kd));
     a.H1 = b.r16(rows, ld16(hmax, kd));
     a.H2 = b.r16(rows, ld16(hmax, kd));
@@ -855,7 +859,7 @@ int td7f_target(int32_t prec, const int32_t *act, const td7f_lin *tenc, const td
     // fp32 with an OUT row wider than CATA's (zs_dim well above actor_hdim):
     // X and CATA side by side, OUT over both (below)
     const bool wide_out = prec == PREC_F32 && old > ld16(a.Ha + a.Z, kd);
-    Bump ba(1);
+    Bump ba;
     a.X = ba.r16(rows, ld16(a.S + a.A, kd));
     if (wide_out) a.CATA = ba.r16(rows, ld16(a.Ha + a.Z, kd));
     a.H1 = ba.r16(rows, ld16(hmax, kd));
@@ -879,7 +883,7 @@ int td7f_target(int32_t prec, const int32_t *act, const td7f_lin *tenc, const td
     }
     a.TW = ba.r32(THIN_NC, tactor[3].n_in);
     a.lds_a = ba.off;
-    Bump bb(1);
+    Bump bb;
     const R16 Xb = bb.r16(rows, ld16(a.S + a.A, kd)), H1b = bb.r16(rows, ld16(hmax, kd)), H2b = bb.r16(rows, ld16(hmax, kd));
     const R16 CATb = bb.r16(rows, ld16(a.Hc + 2 * a.Z, kd));
     const R32 Fb = bb.r32(rows, std::max(hmax, 16));
@@ -919,7 +923,7 @@ int td7f_fixed(int32_t prec, const int32_t *act, const td7f_lin *fenc, const flo
     const int rows = TR;
     int hmax = 0;
     for (int i = 0; i < 6; ++i) hmax = std::max(hmax, fenc[i].n_out);
-    Bump b(1);
+    Bump b;
     a.X = b.r16(rows, ld16(a.S, kd));
     a.H1 = b.r16(rows, ld16(hmax, kd));
     a.H2 = b.r16(rows, ld16(hmax, kd));

@@ -39,14 +39,15 @@ struct XT {
 // dX over the window [c0, c1) (c0 % 16 == 0) of layer L from the dP image a;
 // act'(Y) from global y (row stride yld) when act != ACT_NONE.  Ends with a barrier.
 template <int P, int TH>
-__device__ __forceinline__ void layer_bwd(char *lds, u32x4 (&R)[PD][TH], R16 a, const Lin &L, int c0, int c1,
+__device__ __forceinline__ void layer_bwd(char *lds, Ring<TH> &R, R16 a, const Lin &L, int c0, int c1,
                                           const GDesc *next, int act, const float *y, long yld, R32 o32, float *g,
                                           long gld, R16 o16, float *part, int row0, int nrows, int &si) {
     FSTAMP(si);
-    floatx4 acc[1][TH], yv[1][TH];
+    floatx4 acc[1][os_of(TH)], yv[1][os_of(TH)];
     const GDesc gd{L.wb, L.ksb, c0 / 16};
     gemm<P, 1, TH>(lds, a.off, a.ld, gd, R, acc, next,
-                   EpiSrc{act != ACT_NONE ? y : nullptr, yld, c0, row0, nrows, c1 - c0}, yv);
+                   EpiSrc{act != ACT_NONE ? y : nullptr, yld, c0, row0, nrows, c1 - c0}, yv,
+                   epi_aliases(a, TR, o16, o32));
     FSTAMP(si);
     epi_bwd<P, 1, TH>(lds, acc, c0 / 16, c0, c1, act, yv, o32, g, gld, o16, part, row0, nrows);
     __syncthreads();
@@ -99,7 +100,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     float *y1 = a.y1 + (long)h * B * Hc, *y2 = a.y2 + (long)h * B * Hc;
     int si = 0;
     FSTAMP(si);
-    u32x4 R[PD][TH];
+    Ring<TH> R;
     const long Bp = (long)gridDim.x * TR;
     if (a.phase == 2) {
         // the forward's state back into LDS (the same fp32 values), the ring
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
         }
         const float qv = threadIdx.x < TR ? ldg(a.qs + h * Bp + row0 + threadIdx.x) : 0.f;
         const float mv = threadIdx.x < TR ? ldg(a.ms + h * Bp + row0 + threadIdx.x) : 0.f;
-        ring_fill(R, bwd_of(cr[6], 0));
+        ring_fill<TH>(R, bwd_of(cr[6], 0));
         zero_lds(lds, a.lds_bytes);
         __syncthreads();
 #pragma unroll
@@ -135,7 +136,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     row_issue(sz, a.zsa, Z, Z, row0, B);
     row_issue(szs, a.zs, Z, Z, row0, B);
     thin_issue(tw, cr[6].w, cr[6].ldw, 0, false, 1, cr[6].K);
-    ring_fill(R, fwd_of(cr[0]));
+    ring_fill<TH>(R, fwd_of(cr[0]));
     zero_lds(lds, a.lds_bytes);
     __syncthreads();
     row_put16<P>(lds, ss, a.X, 0, a.S, row0, B);
@@ -251,8 +252,8 @@ __global__ __launch_bounds__(NTH) void encoder_kernel(EncoderArgs a) {
         row_issue(sa, a.a, a.A, a.A, row0, B);
         row_issue(ss, a.s, a.S, a.S, row0, B);  // put after the next_zs pass
     }
-    u32x4 R[PD][TH];
-    ring_fill(R, fwd_of(a.e[0]));
+    Ring<TH> R;
+    ring_fill<TH>(R, fwd_of(a.e[0]));
     zero_lds(lds, a.lds_bytes);
     __syncthreads();
     if (!split || producer) {
@@ -379,8 +380,8 @@ __global__ __launch_bounds__(NTH) void actor_a_kernel(ActorArgs a) {
     row_issue(ss, a.s, a.S, a.S, row0, B);
     row_issue(szs, a.zs, Z, Z, row0, B);
     thin_issue(tw, a.ac[3].w, a.ac[3].ldw, 0, false, a.A, a.ac[3].K);
-    u32x4 R[PD][TH];
-    ring_fill(R, fwd_of(a.ac[0]));
+    Ring<TH> R;
+    ring_fill<TH>(R, fwd_of(a.ac[0]));
     zero_lds(lds, a.lds);
     __syncthreads();
     row_put16<P>(lds, ss, a.X, 0, a.S, row0, B);
@@ -426,8 +427,8 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     row_issue(sz, a.zsa_out, Z, Z, row0, B);
     row_issue(szs, a.zs, Z, Z, row0, B);
     thin_issue(tw, cr[0].w, cr[0].ldw, a.S, true, a.A, Hc);
-    u32x4 R[PD][TH];
-    ring_fill(R, fwd_of(cr[0]));
+    Ring<TH> R;
+    ring_fill<TH>(R, fwd_of(cr[0]));
     zero_lds(lds, a.lds);
     __syncthreads();
     row_put16<P>(lds, ss, a.X, 0, a.S, row0, B);
@@ -492,8 +493,8 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     row_issue(sh, a.h0, Ha, Ha, row0, B);
     const float m0 = ldg(a.mean0 + min(row0 + (int)(threadIdx.x % TR), B - 1));
     thin_issue(tw, a.fe[3].w, a.fe[3].ldw, Z, true, A, He);
-    u32x4 R[PD][TH];
-    ring_fill(R, bwd_of(a.fe[5], 0));
+    Ring<TH> R;
+    ring_fill<TH>(R, bwd_of(a.fe[5], 0));
     zero_lds(lds, a.lds);
     __syncthreads();
     row_add(d0, d1);
@@ -956,7 +957,7 @@ int td7f_critic_phase(int32_t phase, int32_t prec, const int32_t *act, const td7
     g.phase = phase;
     g.qs = q_ws; g.h0s = h0_ws; g.ms = mean_ws;
     const int kd = kd_of(prec);
-    Bump b(1);
+    Bump b;
     g.X = b.r16(TR, ld16(S + A, kd));
     g.CAT = b.r16(TR, ld16(g.Hc + 2 * g.Z, kd));
     g.H1 = b.r16(TR, ld16(g.Hc, kd));
@@ -1011,7 +1012,7 @@ int td7f_encoder(int32_t prec, const int32_t *act, const td7f_lin *enc, const fl
     g.mse_scale = 2.0f / ((float)B * (float)g.Z);
     g.ld = ld;
     const int w = std::max(g.Z, g.He), kd = kd_of(prec);
-    Bump b(1);
+    Bump b;
     g.X = b.r16(TR, ld16(g.S, kd));
     g.H1 = b.r16(TR, ld16(g.He, kd));
     g.H2 = b.r16(TR, ld16(g.He, kd));
@@ -1081,7 +1082,7 @@ int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *
     }
     g.da = u.da; g.dzsa = u.dzsa; g.ld = ld;
     const int hmax = std::max(g.Ha, std::max(g.He, g.Hc)), kd = kd_of(prec);
-    Bump b(1);
+    Bump b;
     if (phase == 0) {
         g.X = b.r16(TR, ld16(g.S, kd));
         g.CATA = b.r16(TR, ld16(g.Ha + g.Z, kd));

@@ -1,6 +1,6 @@
 """Diagnostic: per-phase cycles of the fused TD7 kernels from in-kernel
 s_memtime stamps (libexo_amd_stamps.so: make -C csrc stamps).  Each fused layer
-stamps [gemm start, gemm end (after the k-group reduction), epilogue end];
+stamps [gemm start, gemm end, epilogue end];
 kernels stamp their start.  Prints the median (over workgroups) cycles between
 consecutive stamps of one launch of each pass.  Never the measured number --
 read the shares."""

@@ -1,9 +1,9 @@
 // Per-layer cost of the fused TD7 layer chain (csrc/td7_fused.h) in isolation:
 // G workgroups each run NL forward layers of 320 x 320 (bf16, ks 10, 20 tiles,
 // TH 5) with distinct packed weights, 16 rows in LDS, like one network pass.
-// MODE 0: layer_fwd (gemm + exchange + ELU epilogue + barrier); MODE 1: gemm
-// (incl. exchange) + barrier, no epilogue; MODE 2: ring streaming only (the
-// same loads, no MFMA / exchange / barrier).  Prints us per launch and the
+// MODE 0: layer_fwd (gemm + ELU epilogue + barrier); MODE 1: gemm + barrier,
+// no epilogue; MODE 2: ring streaming only (the same loads of each wave's
+// owned tiles, no MFMA / barrier).  Prints us per launch and the
 // per-workgroup weight-stream rate.
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../include -I../<pkg>/csrc -o layer_bench layer_bench.hip
 #include "td7_fused.h"
@@ -27,22 +27,22 @@ __global__ __launch_bounds__(NTH) void chain_kernel(Args a, float *sink) {
     int si = 0;
     zero_lds(lds, a.lds);
     __syncthreads();
-    u32x4 R[PD][THH];
-    ring_fill(R, GDesc{a.L[0].wf, a.L[0].ksf, 0});
+    Ring<THH> R;
+    ring_fill<THH>(R, GDesc{a.L[0].wf, a.L[0].ksf, 0});
     if constexpr (MODE == 2) {
         u32x4 x = {0u, 0u, 0u, 0u};
-        const int wv = threadIdx.x >> 6, w = wv % NW, kg = wv / NW, lane = threadIdx.x & 63;
+        const int w = wave_id() % NW, lane = threadIdx.x & 63;
+        static_assert(KS == RD, "one ring round per layer");
 #pragma unroll
         for (int l = 0; l < NL; ++l) {
-            int kb, ke;
-            kgroup_range(KS, kg, kb, ke);
 #pragma unroll
-            for (int p = 0; p < PD; ++p)
+            for (int p = 0; p < RD; ++p)
 #pragma unroll
-                for (int i = 0; i < THH; ++i) {
-                    x ^= R[p][i];
-                    if (l + 1 < NL)
-                        R[p][i] = ldg(a.L[l + 1].wf + ((size_t)(w + NW * i) * KS + kb + p) * 64 + lane);
+                for (int j = 0; j < os_of(THH); ++j) {
+                    const int i = own_slot<THH>(j);
+                    x ^= R[p][j];
+                    if (l + 1 < NL && i < THH)
+                        R[p][j] = ldg(a.L[l + 1].wf + ((size_t)(w + NW * i) * KS + p) * 64 + lane);
                     __builtin_amdgcn_sched_barrier(0);
                 }
         }
@@ -57,9 +57,9 @@ __global__ __launch_bounds__(NTH) void chain_kernel(Args a, float *sink) {
             layer_fwd<PREC_BF16, 1, THH>(lds, R, in, a.L[l], l + 1 < NL ? &nx : nullptr, ACT_ELU, out, 0, NO32,
                                         nullptr, 0, 0, 16, si);
         } else {
-            floatx4 acc[1][THH], bias[1][THH];
+            floatx4 acc[1][os_of(THH)], bias[1][os_of(THH)];
             gemm<PREC_BF16, 1, THH>(lds, in.off, in.ld, GDesc{a.L[l].wf, a.L[l].ksf, 0}, R, acc,
-                                    l + 1 < NL ? &nx : nullptr, EpiSrc{a.L[l].b, 0, 0, 0, 0, N}, bias);
+                                    l + 1 < NL ? &nx : nullptr, EpiSrc{a.L[l].b, 0, 0, 0, 0, N}, bias, false);
             __syncthreads();
             if (acc[0][0][0] == 12345.f) sink[threadIdx.x] = acc[0][1][1] + bias[0][0][0];
         }
@@ -96,10 +96,10 @@ int main() {
     Args a{};
     for (int l = 0; l < NL; ++l) a.L[l] = Lin{w + l * wbytes / 16, nullptr, b, N, K, KS, KS, nullptr, 0};
     const int ld = ((KS + PD - 1) / PD * PD) * 32 + 16;
-    a.A = R16{red_bytes(1, THH), ld};
-    a.B = R16{red_bytes(1, THH) + 16 * ld * 2, ld};
-    a.lds = red_bytes(1, THH) + 2 * 16 * ld * 2;
-    const char *names[3] = {"layer_fwd (gemm+exchange+epilogue)", "gemm+exchange, no epilogue", "ring stream only"};
+    a.A = R16{0, ld};
+    a.B = R16{16 * ld * 2, ld};
+    a.lds = 2 * 16 * ld * 2;
+    const char *names[3] = {"layer_fwd (gemm+epilogue+barrier)", "gemm+barrier, no epilogue", "ring stream only"};
     printf("%-38s %5s %9s %10s %14s\n", "mode", "WGs", "us", "us/layer", "GB/s per WG");
     for (int mode = 0; mode < 3; ++mode)
         for (int G : {64, 256}) {
