@@ -13,6 +13,10 @@
 //                  and zsa inputs, one workgroup per (16 rows, head) (:271-273)
 //   td7f_actor_c : the fixed encoder's zsa backward to the action, tanh' and the
 //                  actor's dX chain
+//   td7f_actor_bc: phases 1 / 2 with the offline TD3+BC term (:272-274): phase 1
+//                  also leaves sum |Q| per (head, row tile), phase 2 sums those
+//                  partials in index order in every workgroup and adds
+//                  d(lmbda mean|Q| mse(actor, a))/d actor before tanh'
 //   td7f_wgrad   : every layer's dW = dP^T X and db of one optimiser phase as
 //                  ONE grouped MFMA launch over the transposed 16-bit operands
 //                  the passes above leave in HBM.
@@ -367,6 +371,11 @@ struct ActorArgs {
     R32 H0, DY, F, TW, TW2;
     int small_off;
     int lds;
+    // the TD3+BC term (BC kernels only, td7f_actor_bc)
+    const float *a_bc;         // [B][A] the batch's (normalised) actions
+    float *qabs;               // [2][row tiles] sum |Q| over a tile's live rows
+    float bc_scale, inv_2b;    // lmbda 2 / (B A), 1 / (2 B)
+    R32 QS, AB;                // phase 2: the partials [2 row tiles], the action rows [16][8]
 };
 
 template <int P, int TH>
@@ -411,7 +420,9 @@ __global__ __launch_bounds__(NTH) void actor_a_kernel(ActorArgs a) {
     layer_fwd<P, 1, TH>(lds, R, a.H2, a.fe[5], (const Lin *)nullptr, ACT_NONE, NO16, 0, NO32, a.zsa_out, Z, row0, B, si);
 }
 
-template <int P, int TH>
+// BC: Q of this head from q3 (as critic_kernel computes it) and the tile's
+// sum |Q| -> a.qabs, before the unchanged backward of the constant dq.
+template <int P, int TH, bool BC>
 __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int row0 = blockIdx.x * TR, B = a.B, Z = a.Z, h = blockIdx.y, Hc = a.Hc;
@@ -427,6 +438,8 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     row_issue(sz, a.zsa_out, Z, Z, row0, B);
     row_issue(szs, a.zs, Z, Z, row0, B);
     thin_issue(tw, cr[0].w, cr[0].ldw, a.S, true, a.A, Hc);
+    ThinStage<1> tq;
+    if constexpr (BC) thin_issue(tq, cr[6].w, cr[6].ldw, 0, false, 1, Hc);
     Ring<TH> R;
     ring_fill<TH>(R, fwd_of(cr[0]));
     zero_lds(lds, a.lds);
@@ -435,7 +448,10 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     row_put16<P>(lds, sa, a.X, a.S, a.A, row0, B);
     row_put16<P>(lds, sz, a.CAT, Hc, Z, row0, B);
     row_put16<P>(lds, szs, a.CAT, Hc + Z, Z, row0, B);
-    if constexpr (P != PREC_F32) thin_put<P>(lds, tw, a.TW, a.A, Hc);
+    if constexpr (P != PREC_F32) {
+        thin_put<P>(lds, tw, a.TW, a.A, Hc);
+        if constexpr (BC) thin_put<P>(lds, tq, a.TW2, 1, Hc);
+    }
     __syncthreads();
     // Q = critic(state, actor, zsa, zs) with the updated critic (:270)
     layer_fwd<P, 1, TH>(lds, R, a.X, cr[0], &cr[2], ACT_NONE, NO16, 0, a.H0, nullptr, 0, row0, B, si);
@@ -443,9 +459,24 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     __syncthreads();
     layer_fwd<P, 1, TH>(lds, R, a.CAT, cr[2], &cr[4], a.act_critic, a.H1, 0, NO32, y1, Hc, row0, B, si);
     // (fp32: the thin weights' region lies in CAT, dead from here on)
-    if constexpr (P == PREC_F32) thin_put<P>(lds, tw, a.TW, a.A, Hc);
+    if constexpr (P == PREC_F32) {
+        thin_put<P>(lds, tw, a.TW, a.A, Hc);
+        if constexpr (BC) thin_put<P>(lds, tq, a.TW2, 1, Hc);
+    }
     const GDesc b3 = bwd_of(cr[6], 0);
     layer_fwd<P, 1, TH>(lds, R, a.H1, cr[4], &b3, a.act_critic, a.H2, 0, NO32, y2, Hc, row0, B, si);
+    if constexpr (BC) {
+        // Q = q3(H2) of this head, then sum |Q| over the tile's live rows in
+        // row order (:273, the |Q| mean's partial): one lane, one store
+        layer_thin_fwd<P, 1>(lds, a.H2, cr[6], a.TW2, ACT_NONE, a.F, TR, nullptr, 0, row0, B, si);
+        if (threadIdx.x == 0) {
+            float sum = 0.f;
+            for (int r = 0; r < TR; ++r)
+                if (row0 + r < B) sum += fabsf(*p32(lds, a.F, r, 0));
+            stg(a.qabs + (long)h * gridDim.x + blockIdx.x, sum);
+        }
+        __syncthreads();
+    }
     // d(-Q.mean())/dQ (:272): the constant -1/(2B) on every live row
     for (int r = threadIdx.x; r < TR; r += NTH) *p32(lds, a.F, r, 0) = a.dq;
     __syncthreads();
@@ -477,7 +508,10 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     }
 }
 
-template <int P, int TH>
+// BC: + c (actor - a) inside the bracket before tanh', c = lmbda mean|Q| 2 / (B A)
+// with mean|Q| from actor_b's partials, summed in index order by every workgroup
+// (the same bits everywhere, no atomics).
+template <int P, int TH, bool BC>
 __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int row0 = blockIdx.x * TR, B = a.B, Z = a.Z, Ha = a.Ha, He = a.He, A = a.A, tile = blockIdx.x;
@@ -493,6 +527,13 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     row_issue(sh, a.h0, Ha, Ha, row0, B);
     const float m0 = ldg(a.mean0 + min(row0 + (int)(threadIdx.x % TR), B - 1));
     thin_issue(tw, a.fe[3].w, a.fe[3].ldw, Z, true, A, He);
+    RowStage sb;
+    const int nq = 2 * (int)gridDim.x;
+    float q0 = 0.f;
+    if constexpr (BC) {
+        row_issue(sb, a.a_bc, A, A, row0, B);
+        q0 = ldg(a.qabs + min((int)threadIdx.x, nq - 1));
+    }
     Ring<TH> R;
     ring_fill<TH>(R, bwd_of(a.fe[5], 0));
     zero_lds(lds, a.lds);
@@ -502,6 +543,11 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     if (threadIdx.x < TR) mean[threadIdx.x] = row0 + (int)threadIdx.x < B ? m0 : 0.f;
     row_put32(lds, sh, a.H0, Ha, row0, B);
     thin_put<P>(lds, tw, a.TW, A, He);
+    if constexpr (BC) {
+        row_put32(lds, sb, a.AB, A, row0, B);
+        if ((int)threadIdx.x < nq) *p32(lds, a.QS, 0, threadIdx.x) = q0;
+        for (int i = threadIdx.x + NTH; i < nq; i += NTH) *p32(lds, a.QS, 0, i) = ldg(a.qabs + i);  // B > 4,096
+    }
     __syncthreads();
     const GDesc nx10 = bwd_of(a.fe[4], 0);
     layer_bwd<P, TH>(lds, R, a.DP0, a.fe[5], 0, He, &nx10, a.act_enc, a.yz[1], He, NO32, nullptr, 0, a.DP1, nullptr,
@@ -514,12 +560,22 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     thin<P, THIN_NC>(lds, a.DP0, 0, He, a.TW, A, a.F, 1.f / Ty<P>::gs);
     __syncthreads();
     FSTAMP(si);
+    float cbc = 0.f;
+    if constexpr (BC) {
+        if ((int)threadIdx.x < TR * A) {  // the lanes of the loop below: LDS broadcast reads, index order
+            float sum = 0.f;
+            for (int i = 0; i < nq; ++i) sum += *p32(lds, a.QS, 0, i);
+            cbc = a.bc_scale * (sum * a.inv_2b);
+        }
+    }
     for (int k = threadIdx.x; k < TR * A; k += NTH) {
         const int r = k / A, c = k - r * A, b = row0 + r;
         float v = 0.f;
         if (b < B) {
             const float y = ldg(a.act_out + (long)b * A + c);
-            v = (*p32(lds, a.F, r, c) + ldg(a.da + (long)b * A + c) + ldg(a.da + ((long)B + b) * A + c)) * (1.f - y * y);
+            float d = *p32(lds, a.F, r, c) + ldg(a.da + (long)b * A + c) + ldg(a.da + ((long)B + b) * A + c);
+            if constexpr (BC) d += cbc * (y - *p32(lds, a.AB, r, c));
+            v = d * (1.f - y * y);
         }
         *p32(lds, a.F, r, c) = v;
     }
@@ -903,6 +959,14 @@ static bool alias32(R16 a, R16 b, int n, R32 &d) {
     d = R32{a.off, n};
     return a.off + TR * n * 4 <= b.off + TR * b.ld * 2;
 }
+// DISPATCH with a third (bool) template argument
+#define DISPATCH_F(PREC, TH, KERNEL, F, ...)                                                              \
+    ((PREC) == PREC_BF16  ? ((TH) == 5 ? launch(KERNEL<PREC_BF16, 5, F>, __VA_ARGS__)                     \
+                                       : launch(KERNEL<PREC_BF16, 4, F>, __VA_ARGS__))                    \
+     : (PREC) == PREC_F16 ? ((TH) == 5 ? launch(KERNEL<PREC_F16, 5, F>, __VA_ARGS__)                      \
+                                       : launch(KERNEL<PREC_F16, 4, F>, __VA_ARGS__))                     \
+                          : ((TH) == 5 ? launch(KERNEL<PREC_F32, 5, F>, __VA_ARGS__)                      \
+                                       : launch(KERNEL<PREC_F32, 4, F>, __VA_ARGS__)))
 static bool wb_ok(const td7f_lin *l, int n) {
     for (int i = 0; i < n; ++i)
         if (!l[i].wb || l[i].ksb <= 0 || l[i].ksb % PD) return false;
@@ -1037,9 +1101,11 @@ int td7f_encoder(int32_t prec, const int32_t *act, const td7f_lin *enc, const fl
     return DISPATCH(prec, th, encoder_kernel, dim3((B + TR - 1) / TR, nz_ws ? 2 : 1), b.off, g, (hipStream_t)stream);
 }
 
-int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *actor, const td7f_lin *fenc,
-               const td7f_lin *critic, const float *s, const float *zs, int32_t B, const td7f_actor_bufs *bufs,
-               const td7f_xt *xt, int64_t ld, void *stream) {
+// td7f_actor (bc == false) and td7f_actor_bc's phases 1 / 2 (bc == true)
+static int actor_pass(bool bc, int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *actor,
+                      const td7f_lin *fenc, const td7f_lin *critic, const float *s, const float *zs, const float *a_bc,
+                      float lmbda, float *qabs, int32_t B, const td7f_actor_bufs *bufs, const td7f_xt *xt, int64_t ld,
+                      void *stream) {
     if (!prec_ok(prec) || phase < 0 || phase > 2 || !act || !actor || !fenc || !critic || !s || !zs || !bufs || !xt ||
         B <= 0 || ld < B || ld % 32)
         return EXO_EINVAL;
@@ -1081,6 +1147,13 @@ int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *
         g.yc[i] = u.yc[i];
     }
     g.da = u.da; g.dzsa = u.dzsa; g.ld = ld;
+    const int tiles = (B + TR - 1) / TR;
+    if (bc) {
+        g.a_bc = a_bc;
+        g.qabs = qabs;
+        g.bc_scale = lmbda * 2.0f / ((float)B * (float)g.A);
+        g.inv_2b = 1.0f / (2.0f * (float)B);
+    }
     const int hmax = std::max(g.Ha, std::max(g.He, g.Hc)), kd = kd_of(prec);
     Bump b;
     if (phase == 0) {
@@ -1101,9 +1174,11 @@ int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *
             // fp32 (as td7f_critic): dP images and the thin weights (staged
             // after q1's forward) in CAT, dY over H1 | H2
             if (!alias_pair(g.CAT, ld16(g.Hc, kd), g.DP0, g.DP1) || !alias32(g.H1, g.H2, g.Hc, g.DY)) return EXO_EINVAL;
+            // (BC: q3's row behind them)
             const int tw = g.DP1.off + round_up(TR * g.DP1.ld * 2, 16);
             g.TW = R32{tw, g.Hc};
-            if (tw + THIN_NC * g.Hc * 4 > g.CAT.off + TR * g.CAT.ld * 2) return EXO_EINVAL;
+            g.TW2 = R32{tw + THIN_NC * g.Hc * 4, g.Hc};
+            if (tw + (THIN_NC + (bc ? 1 : 0)) * g.Hc * 4 > g.CAT.off + TR * g.CAT.ld * 2) return EXO_EINVAL;
         } else {
             g.DP0 = b.r16(TR, ld16(g.Hc));
             g.DP1 = b.r16(TR, ld16(g.Hc));
@@ -1112,6 +1187,7 @@ int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *
         if (prec != PREC_F32) g.DY = b.r32(TR, g.Hc);
         g.F = b.r32(TR, 16);
         if (prec != PREC_F32) g.TW = b.r32(THIN_NC, g.Hc);
+        if (prec != PREC_F32 && bc) g.TW2 = b.r32(1, g.Hc);
     } else {
         g.DP0 = b.r16(TR, ld16(std::max(hmax, g.Z), kd));
         g.DP1 = b.r16(TR, ld16(std::max(hmax, g.Z), kd));
@@ -1119,15 +1195,37 @@ int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *
         g.DY = b.r32(TR, g.Ha);
         g.F = b.r32(TR, 16);
         g.TW = b.r32(THIN_NC, g.He);
+        if (bc) {
+            g.AB = b.r32(TR, THIN_NC);
+            g.QS = b.r32(1, 2 * tiles);
+        }
     }
     const R32 sm = b.r32(1, 2 * TR);
     g.small_off = sm.off;
     g.lds = b.off;
     const hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((B + TR - 1) / TR, phase == 1 ? 2 : 1);
+    const dim3 grid(tiles, phase == 1 ? 2 : 1);
     if (phase == 0) return DISPATCH(prec, th, actor_a_kernel, grid, b.off, g, st);
-    if (phase == 1) return DISPATCH(prec, th, actor_b_kernel, grid, b.off, g, st);
-    return DISPATCH(prec, th, actor_c_kernel, grid, b.off, g, st);
+    if (phase == 1)
+        return bc ? DISPATCH_F(prec, th, actor_b_kernel, true, grid, b.off, g, st)
+                  : DISPATCH_F(prec, th, actor_b_kernel, false, grid, b.off, g, st);
+    return bc ? DISPATCH_F(prec, th, actor_c_kernel, true, grid, b.off, g, st)
+              : DISPATCH_F(prec, th, actor_c_kernel, false, grid, b.off, g, st);
+}
+
+int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *actor, const td7f_lin *fenc,
+               const td7f_lin *critic, const float *s, const float *zs, int32_t B, const td7f_actor_bufs *bufs,
+               const td7f_xt *xt, int64_t ld, void *stream) {
+    return actor_pass(false, prec, phase, act, actor, fenc, critic, s, zs, nullptr, 0.f, nullptr, B, bufs, xt, ld,
+                      stream);
+}
+
+int td7f_actor_bc(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *actor, const td7f_lin *fenc,
+                  const td7f_lin *critic, const float *s, const float *zs, const float *a, float lmbda, float *qabs,
+                  int32_t B, const td7f_actor_bufs *bufs, const td7f_xt *xt, int64_t ld, void *stream) {
+    if (phase != 0 && (!a || !qabs)) return EXO_EINVAL;
+    return actor_pass(phase != 0, prec, phase, act, actor, fenc, critic, s, zs, a, lmbda, qabs, B, bufs, xt, ld,
+                      stream);
 }
 
 static int wgrad_args(int32_t prec, int32_t njobs, const td7f_wg_job *jobs, int64_t ld, int32_t rows,

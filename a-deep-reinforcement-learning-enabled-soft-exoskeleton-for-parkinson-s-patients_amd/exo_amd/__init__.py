@@ -14,3 +14,11 @@ import os as _os
 _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 
 from .vec_env import VecExoskeletonEnv, DEFAULTS, draws_per_episode  # noqa: F401
+
+
+def __getattr__(name):
+    # the offline trainer (exo_amd.rollout imports the TD7 stack: on first use)
+    if name == "OfflineTrainer":
+        from .rollout import OfflineTrainer
+        return OfflineTrainer
+    raise AttributeError(f"module 'exo_amd' has no attribute {name!r}")

@@ -249,6 +249,9 @@ EXPORTS = {
                                P(TD7FXT), ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "td7f_actor": (c_int32, [c_int32, c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), P(TD7FLin), c_void_p, c_void_p,
                              c_int32, P(TD7FActorBufs), P(TD7FXT), ctypes.c_int64, c_void_p]),
+    "td7f_actor_bc": (c_int32, [c_int32, c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), P(TD7FLin), c_void_p, c_void_p,
+                                c_void_p, ctypes.c_float, c_void_p, c_int32, P(TD7FActorBufs), P(TD7FXT),
+                                ctypes.c_int64, c_void_p]),
     "td7f_wgrad": (c_int32, [c_int32, c_int32, P(TD7FWgJob), ctypes.c_int64, c_int32, c_void_p, c_void_p, c_int32,
                              ctypes.c_float, ctypes.c_float, c_void_p]),
     "td7f_wgrad_adam": (c_int32, [c_int32, c_int32, P(TD7FWgJob), ctypes.c_int64, c_int32, c_void_p, c_void_p,

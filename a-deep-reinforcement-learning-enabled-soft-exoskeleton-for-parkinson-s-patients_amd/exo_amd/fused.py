@@ -207,6 +207,8 @@ class FusedNets:
                     t.critic(s, a, zs, zsa, torch.zeros((B, 2), **f32), one, one, phase=ph)
                 for ph in (0, 1, 2):
                     t.actor(ph, s, zs)
+                for ph in (1, 2):  # the offline (TD3+BC) variants
+                    t.actor(ph, s, zs, action=a, lmbda=0.1)
                 self.train_ok = True
             except RuntimeError as e:  # inference fused, the update per layer
                 self.train_error = str(e)
@@ -479,6 +481,8 @@ class FusedTrain:
         self.yc = [torch.zeros((2, B, Hc), **f32) for _ in range(2)]
         self.da = torch.zeros((2, B, A), **f32)
         self.dzsa = torch.zeros((2, B, Z), **f32)
+        # offline (TD3+BC): sum |Q| per (head, row tile), actor(1) -> actor(2)
+        self.qabs = torch.zeros((2, -(-B // 16)), **f32)
         P = ctypes.c_void_p
         self.actor_bufs = nat.TD7FActorBufs(self.act_out.data_ptr(), self.zsa_out.data_ptr(), self.h0.data_ptr(),
                                             self.mean0.data_ptr(), (P * 2)(*[t.data_ptr() for t in self.ya]),
@@ -611,9 +615,19 @@ class FusedTrain:
                     nat.ptr(self.prio), self.B)
         return self.prio
 
-    def actor(self, phase, state, zs):
+    def actor(self, phase, state, zs, action=None, lmbda=0.0):
+        """td7f_actor; action given: td7f_actor_bc, the offline update's TD3+BC
+        term lmbda |Q|.mean() mse(actor, action) with it (phase 1 leaves the
+        |Q| partials in self.qabs, phase 2 reads them and the batch actions)."""
         fz = self.nets
         fz.refresh("actor", "fixed_encoder", "critic")
+        if action is not None:
+            nat.check(nat.lib().td7f_actor_bc(fz.prec, phase, fz.act, fz.nets["actor"].array,
+                                              fz.nets["fixed_encoder"].array, fz.nets["critic"].array, nat.ptr(state),
+                                              nat.ptr(zs), nat.ptr(action), float(lmbda), nat.ptr(self.qabs), self.B,
+                                              ctypes.byref(self.actor_bufs), self._xts(self.xt_actor), self.ld,
+                                              nat.stream_ptr(state.device)), f"td7f_actor_bc[{phase}]")
+            return
         nat.check(nat.lib().td7f_actor(fz.prec, phase, fz.act, fz.nets["actor"].array, fz.nets["fixed_encoder"].array,
                                        fz.nets["critic"].array, nat.ptr(state), nat.ptr(zs), self.B,
                                        ctypes.byref(self.actor_bufs), self._xts(self.xt_actor), self.ld,

@@ -157,6 +157,71 @@ class LAP:
                                             nat.ptr(act), float(self.normalize_actions), n, nat.ptr(self._row_ws),
                                             self._stream()), "lap_store_batch")
 
+    # ------------------------------------------------------ datasets (offline)
+    def load_dataset(self, state, action, next_state, reward, done, strata, chunk=65536):
+        """A dataset of transitions (numpy or torch, host or device; row i to
+        stratum strata[i]) through add_batch in row order: ring semantics per
+        stratum (a stratum given more rows than max_size keeps the newest),
+        priority max_priority, actions divided by normalize_actions.  Chunks
+        hold at most `chunk` rows and at most max_size rows of one stratum
+        (one add_batch call must not wrap a ring onto itself).  ValueError if
+        a stratum is empty afterwards: sample() draws batch_size rows from
+        every stratum.  One host read of the ring sizes at the end."""
+        cpu = lambda t: torch.as_tensor(t)  # noqa: E731
+        sr = cpu(strata).to(torch.int64).reshape(-1).cpu()
+        n = sr.numel()
+        if n and (int(sr.min()) < 0 or int(sr.max()) >= self.num_envs):
+            raise ValueError(f"load_dataset: strata outside 0..{self.num_envs - 1}")
+        cols = [cpu(state).reshape(n, self.state_dim), cpu(action).reshape(n, self.action_dim),
+                cpu(next_state).reshape(n, self.state_dim), cpu(reward).reshape(n), cpu(done).reshape(n)]
+        cols[4] = cols[4].to(torch.uint8) if cols[4].dtype != torch.bool else cols[4]
+        for lo, hi in self._dataset_chunks(sr, int(chunk)):
+            s, a, s2, r, d = (c[lo:hi].to(self.device) for c in cols)
+            self.add_batch(s, a, s2, r, d, sr[lo:hi].to(device=self.device, dtype=torch.int32))
+        empty = (self.size_s == 0).nonzero().reshape(-1).tolist()
+        if empty:
+            raise ValueError(f"load_dataset: no rows for strata {empty} (every stratum is sampled)")
+
+    def _dataset_chunks(self, strata, chunk):
+        """[lo, hi) row ranges of load_dataset: <= chunk rows, <= max_size rows of one stratum."""
+        n, C = strata.numel(), self.max_size
+        if n == 0:
+            return []
+        # rank of every row inside its stratum, in row order
+        rank = torch.zeros(n, dtype=torch.int64)
+        for s in range(self.num_envs):
+            m = strata == s
+            rank[m] = torch.arange(int(m.sum()))
+        out, lo = [], 0
+        base = torch.zeros(self.num_envs, dtype=torch.int64)  # ranks at the chunk's start
+        while lo < n:
+            hi = min(lo + max(chunk, 1), n)
+            over = (rank[lo:hi] - base[strata[lo:hi]] >= C).nonzero()
+            if over.numel():
+                hi = lo + int(over[0])
+            out.append((lo, hi))
+            base.scatter_reduce_(0, strata[lo:hi], rank[lo:hi] + 1, "amax")
+            lo = hi
+        return out
+
+    def export_dataset(self):
+        """The rows the per-stratum rings hold, oldest first per stratum (after
+        a wrap too), as CPU tensors: state, action (de-normalised), next_state,
+        reward [n], done [n] (uint8), strata [n] (int32).  load_dataset(**it)
+        into a fresh buffer of the same capacity holds the same rows."""
+        C = self.max_size
+        size, ptr = self.size_s.cpu().tolist(), self.ptr_s.cpu().tolist()
+        rows, strata = [], []
+        for s in range(self.num_envs):
+            slots = (ptr[s] - size[s] + torch.arange(size[s], dtype=torch.int64)) % C
+            rows.append(s * (C + 1) + slots)
+            strata.append(torch.full((size[s],), s, dtype=torch.int32))
+        rows = torch.cat(rows).to(self.device)
+        take = lambda t: t.reshape(-1, t.shape[-1]).index_select(0, rows).cpu()  # noqa: E731
+        return dict(state=take(self.state), action=take(self.action) * self.normalize_actions,
+                    next_state=take(self.next_state), reward=take(self.reward).reshape(-1),
+                    done=(1.0 - take(self.not_done).reshape(-1)).to(torch.uint8), strata=torch.cat(strata))
+
     def add_batch_ref(self, state, action, next_state, reward, done, strata, active=None, advance=None):
         """LAP.add (:49-63) for every active row in row order -- the training
         script's per-env loop over one vectorised step -- with the reference's

@@ -1645,3 +1645,124 @@ class RefScheduleTrainer(VecTrainer):
                                checkpoint_refreshed=ag.checkpoint_refreshes > refreshed,
                                steps_count=self.steps_count))
         return self.round_env_steps, burst
+
+
+class OfflineTrainer:
+    """Offline TD7(+BC) on a loaded dataset (Agent(..., offline=True) after
+    Agent.load_dataset / LAP.load_dataset): Agent.train() step after step
+    without an env, as graph replays.
+
+    One step(): the update on the current batch slot (TD7Learner.phase_grads /
+    phase_steps), the LAP priority update and the next step's sample into the
+    other slot as one launch (LAP.update_priority_and_sample, bit-identical to
+    update_priority + sample: tests/test_lap_update_sample_chain_gpu.py), the
+    actor phases every policy_freq steps -- the same launches on the same
+    values as Agent.train() (the next sample is drawn before the target
+    refresh instead of after it; it reads neither the nets nor max_priority).
+    One captured graph per (update_actor, slot); the target refresh
+    (update_targets_device, then reset_max_priority) is a graph of its own,
+    captured with the first of them.  Graph lifetime as the other trainers':
+    new_graph / capture, and retire_graphs(trainer) (= release_graphs()) when
+    done ("The graph-replay crash").  One GPU only.
+
+    Not here: the overlapped pairs, the target prefetch and the
+    encoder step on its branch (TD7Learner.defer_side_join) of VecTrainer."""
+
+    def __init__(self, agent, use_graphs=True, warmup_eager=2):
+        if agent.sync.world > 1:
+            raise ValueError("OfflineTrainer: one GPU only (data parallel offline training is not implemented)")
+        self.agent = agent
+        self.device = agent.device
+        self.use_graphs = bool(use_graphs)
+        self.warmup_eager = int(warmup_eager)
+        self.graphs = {}
+        self._refresh_graph = None
+        self.iters = 0
+        self.refreshes = 0
+        self._slot = 0
+        rb = agent.replay_buffer
+        if int((rb.size_s == 0).sum()):
+            raise ValueError("OfflineTrainer: a stratum of the replay is empty (load a dataset first)")
+        if self.use_graphs:
+            graph_reductions_ok(self.device)
+        rb.sample(slot=0)
+
+    def _iteration(self, update_actor, slot):
+        """Agent.train()'s device work of one step on the batch in `slot`."""
+        ag, L, rb = self.agent, self.agent.learner, self.agent.replay_buffer
+        batch, ind = rb._slot(slot)
+        L.drop_prefetch()
+        L.pre_in = None
+        L.defer_side_join = False  # every branch joined inside the step
+        L.prefetch_actor = bool(update_actor)
+        priority = L.phase_grads(*batch)
+        L.phase_steps()
+        rb.update_priority_and_sample(priority, ind, 1 - slot)
+        if update_actor:
+            L.phase_actor_grads(batch[0], batch[1])
+            L.phase_actor_step()
+        L.prefetch_actor = False
+        L.join_side()
+
+    def _capture(self, key):
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        g = new_graph()
+        with torch.cuda.stream(s):
+            with capture(g, stream=s), ForkJoinAudit(s):
+                self._iteration(*key)
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self.graphs[key] = g
+        if self._refresh_graph is None:
+            self._capture_refresh()
+
+    def _capture_refresh(self):
+        """Record (not run) the target refresh (VecTrainer._capture_refresh)."""
+        ag, L = self.agent, self.agent.learner
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        g = new_graph()
+        with torch.cuda.stream(s):
+            with capture(g, stream=s, capture_error_mode="thread_local"), ForkJoinAudit(s):
+                L.update_targets_device()
+                ag.replay_buffer.reset_max_priority()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self._refresh_graph = g
+
+    def _refresh_targets(self):
+        ag, L = self.agent, self.agent.learner
+        if L.training_steps % L.hp.target_update_rate != 0:
+            return False
+        self.refreshes += 1
+        if self.use_graphs and self._refresh_graph is not None:
+            L.drop_prefetch()
+            self._refresh_graph.replay()
+            return True
+        L.maybe_update_targets()
+        ag.replay_buffer.reset_max_priority()
+        return True
+
+    def step(self):
+        """One Agent.train() (TD7_multi_agent.py:211-293)."""
+        ag, L = self.agent, self.agent.learner
+        L.training_steps += 1
+        update_actor = L.training_steps % ag.hp.policy_freq == 0
+        key = (update_actor, self._slot)
+        # every policy-update parity runs eagerly once before its capture
+        if not self.use_graphs or self.iters < max(self.warmup_eager, int(ag.hp.policy_freq)):
+            self._iteration(*key)
+        else:
+            if key not in self.graphs:
+                self._capture(key)
+            self.graphs[key].replay()
+        self._slot ^= 1
+        self._refresh_targets()
+        self.iters += 1
+
+    def run(self, n):
+        for _ in range(int(n)):
+            self.step()
+
+    def release_graphs(self):
+        """retire_graphs(self): destroy the captured graphs (synchronises)."""
+        return retire_graphs(self)

@@ -72,6 +72,9 @@ ENC_STEP_BRANCH = os.environ.get("EXO_ENC_STEP_BRANCH", "1") != "0"
 # ...and every optimiser step (encoder, critic, actor) inside its weight-gradient
 # launch (td7f_wgrad_adam); EXO_WGRAD_ADAM=0: separate td7f_adam_pack launches
 WGRAD_ADAM = os.environ.get("EXO_WGRAD_ADAM", "1") != "0"
+# the offline (TD3+BC) actor update in the fused actor passes (td7f_actor_bc);
+# EXO_OFFLINE_FUSED=0: the torch-autograd branch, as before the fused BC term
+OFFLINE_FUSED = os.environ.get("EXO_OFFLINE_FUSED", "1") != "0"
 
 
 @dataclass
@@ -1175,7 +1178,11 @@ class TD7Learner:
 
     def phase_actor_grads(self, state, action):
         """:268-277 with the just-updated critic."""
-        if self.fused_train and state.is_cuda and not self.offline:
+        # offline (the TD3+BC term, :272-274): fused too on one GPU; under data
+        # parallelism the |Q| mean is global and would need a collective
+        # between phases 1 and 2 -- the autograd branch below
+        bc = self.offline
+        if self.fused_train and state.is_cuda and not (bc and (self.sync.active or not OFFLINE_FUSED)):
             # fused: actor forward (unless prefetched on its branch), the critic
             # heads back to the action / zsa inputs, the zsa and actor backward,
             # then the actor's weight gradients (one grouped launch)
@@ -1184,8 +1191,13 @@ class TD7Learner:
             if not getattr(self, "_actor_fused_pre", False):
                 tr.actor(0, st, self._fixed_zs)
             self._actor_fused_pre = False
-            tr.actor(1, st, self._fixed_zs)
-            tr.actor(2, st, self._fixed_zs)
+            if bc:
+                act = action.contiguous()
+                tr.actor(1, st, self._fixed_zs, action=act, lmbda=self.hp.lmbda)
+                tr.actor(2, st, self._fixed_zs, action=act, lmbda=self.hp.lmbda)
+            else:
+                tr.actor(1, st, self._fixed_zs)
+                tr.actor(2, st, self._fixed_zs)
             # graph-replayed trainer on one GPU: the actor's optimiser step and
             # repack in the weight-gradient launch (phase_actor_step has nothing left)
             self._actor_step_done = (self.defer_side_join and WGRAD_ADAM and ADAM_PACK and not self.sync.active
@@ -1213,10 +1225,14 @@ class TD7Learner:
             # Q directly (a cached tensor in Q's strides, no loss kernels)
             grads = torch.autograd.grad(Q, params, grad_outputs=self._neg_mean_grad(Q))
         else:
-            actor_loss = -Q.float().mean()
+            # the loss in fp32 (autocast outputs cast up), in fp64 when Q is
+            # (the fp64 restatement of this branch): no cast of fp64 values
+            lt = torch.float64 if Q.dtype == torch.float64 else torch.float32
+            Ql = Q.to(lt)
+            actor_loss = -Ql.mean()
             if self.offline:
-                actor_loss = actor_loss + self.hp.lmbda * Q.float().abs().mean().detach() * F.mse_loss(actor.float(),
-                                                                                                   action)
+                actor_loss = actor_loss + self.hp.lmbda * Ql.abs().mean().detach() * F.mse_loss(actor.to(lt),
+                                                                                                action.to(lt))
             grads = torch.autograd.grad(actor_loss, params)
         for p, g in zip(params, grads):
             if p.grad is None:
@@ -1506,6 +1522,16 @@ class Agent:
         if self.learner.maybe_update_targets():
             self.replay_buffer.reset_max_priority()
             self.sync.max_(self.replay_buffer._maxp)  # :120 over every rank's leaves
+
+    # ---------------------------------------------------------- datasets
+    def save_dataset(self, path):
+        """The replay's transitions (LAP.export_dataset) as a torch.save file."""
+        torch.save(self.replay_buffer.export_dataset(), path)
+
+    def load_dataset(self, path, chunk=65536):
+        """A save_dataset file (a dict of tensors: state, action, next_state,
+        reward, done, strata) into the replay (LAP.load_dataset)."""
+        self.replay_buffer.load_dataset(**torch.load(path, weights_only=True), chunk=chunk)
 
     def maybe_train_and_checkpoint(self, ep_timesteps, ep_return, train=None):
         """:296-312 (the episode return is MIN-reduced over data-parallel ranks).

@@ -797,6 +797,19 @@ typedef struct {
 int td7f_actor(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *actor, const td7f_lin *fenc,
                const td7f_lin *critic, const float *s_dev, const float *zs_dev, int32_t B,
                const td7f_actor_bufs *bufs, const td7f_xt *xt, int64_t ld, void *stream);
+/* The offline actor update (TD7_multi_agent.py:266-277 with offline=True): the
+ * TD3+BC line `actor_loss + lmbda * Q.abs().mean().detach() * F.mse_loss(actor,
+ * action)` (:272-274) inside the same three launches.  Phase 0 is td7f_actor's
+ * phase 0.  Phase 1 also computes each head's Q and writes qabs_dev
+ * [2][ceil(B/16)] fp32: sum |Q| over the live rows of (head, row tile), in row
+ * order.  Phase 2 reads it (every workgroup sums the partials in index order:
+ * no atomics, the same bits everywhere) and the batch's normalised actions
+ * a_dev [B][A], and adds lmbda * mean|Q| * 2 (actor - a) / (B A) to d actor
+ * before tanh'.  a_dev and qabs_dev must not be NULL in phases 1 and 2. */
+int td7f_actor_bc(int32_t prec, int32_t phase, const int32_t *act, const td7f_lin *actor, const td7f_lin *fenc,
+                  const td7f_lin *critic, const float *s_dev, const float *zs_dev, const float *a_dev, float lmbda,
+                  float *qabs_dev, int32_t B, const td7f_actor_bufs *bufs, const td7f_xt *xt, int64_t ld,
+                  void *stream);
 /* dW = dP^T X / gs -> dw [n][k] (fp32, row stride k) and db = the column
  * partials summed over row_tiles (when db is not NULL), for njobs layers in one
  * launch; rows = the reduction length (multiple of 32).  prio_dev not NULL:
