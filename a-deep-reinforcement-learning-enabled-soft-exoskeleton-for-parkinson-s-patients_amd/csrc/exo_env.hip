@@ -1391,6 +1391,31 @@ int exo_set_seed(exo_ctx *c, uint64_t seed) {
     return EXO_OK;
 }
 
+int exo_restart(exo_ctx *c, uint64_t seed, void *stream) {
+    if (!c) return EXO_EINVAL;
+    if (c->physics != EXO_PHYS_IDEAL) return fail(c, EXO_EINVAL, "exo_restart: ideal physics only");
+    DeviceGuard g(c->device);
+    const size_t N = c->N;
+    const hipStream_t s = (hipStream_t)stream;
+    Dev &S = c->S;
+    // what a reset carries over from the episode before it (the arm pose, the
+    // reference, the previous actions) and the draw key's episode index, as
+    // exo_create allocates them; then the constructor's own reset.  The carry
+    // of a budgeted step (S.rk, exo_set_step_budget) is left as it is: the
+    // reset clears every env's pend flag, and a carry is read only under it.
+    hipError_t e = hipMemsetAsync(S.episode, 0, N * sizeof(uint32_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.counts, 0, N * sizeof(int32_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.phys_q, 0, 5 * N * sizeof(double), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.ref, 0, 6 * N * sizeof(double), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.posv, 0, 21 * N * sizeof(float), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.prev_a, 0, 7 * N * sizeof(double), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.prev2_a, 0, 7 * N * sizeof(double), s);
+    if (e == hipSuccess) e = hipMemsetAsync(S.viol, 0, N * sizeof(int32_t), s);
+    if (int rc = check(c, e, "exo_restart")) return rc;
+    c->seed = seed;
+    return exo_reset(c, nullptr, c->obs_scratch, stream);
+}
+
 int exo_tremor_metrics(exo_ctx *c, const float *info_dev, const uint8_t *stepped_dev, double humerus_length,
                        double forearm_length, double hand_length, int32_t disregard, float *metrics_dev,
                        float *counters_dev, void *stream) {

@@ -1,0 +1,228 @@
+// td7_fused_multi.hip -- select_action of several policies in one launch.
+//
+//   td7f_select_multi : Agent.select_action (Agent/TD7_multi_agent.py:192-209,
+//                       Agent/TD7_multi_agent_Pink_noise.py:212-214) for npol
+//                       policies at once: policy p acts on the contiguous rows
+//                       [seg[p], seg[p+1]) of obs.
+//
+// An evaluation of K policies over a few hundred envs each is K launches of a
+// few dozen workgroups on 256 CUs; here the K row ranges are one grid.  The
+// per-row arithmetic is select_kernel's (td7_fused.hip, 16-row tiles), built
+// from the same blocks of td7_fused.h; what differs is where a workgroup gets
+// its work from:
+//
+//   tile table   int32 [ntiles][3] = (policy, row0, row_end), indexed by
+//                blockIdx.x.  A tile never straddles a segment (a workgroup
+//                streams ONE policy's weights): a segment of len rows has
+//                ceil(len / 16) tiles, the last one ragged.  row_end plays the
+//                part select_kernel's a.n plays: rows >= row_end are neither
+//                read nor written.
+//   policy table td7f_lin [npol][7] = zs1..zs3, l0..l3 of each policy, in
+//                device memory (seven Lins x 15 policies do not fit the kernel
+//                arguments).  Pointers and shapes only: repacking a policy's
+//                weights in place keeps it valid.
+//
+// Both tables are read with wave-uniform (scalar) loads: the addresses depend
+// on blockIdx.x alone and nothing in the kernel stores to global memory before
+// its last stage.
+#include "td7_fused.h"
+
+#include <algorithm>
+
+namespace td7f {
+
+struct SelectMultiArgs {
+    const td7f_lin *pol;  // device [npol][7]
+    const int *tiles;     // device [ntiles][3]
+    int act_enc, act_actor;
+    const float *obs;
+    int S, A, Z, Ha;
+    float *out;
+    Noise nz;
+    int noisy;    // 0: deterministic (nz unused, no noise state touched)
+    float scale;  // deterministic mode's max_action
+    R16 X, H1, H2, CAT;
+    R32 F, TW, FT;
+    int lds_bytes;
+};
+
+// a wave-uniform 32-bit word as a scalar (the compiler folds it when the load
+// already is one)
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+template <typename T>
+__device__ __forceinline__ T *uni_ptr(const uint32_t *w) {
+    return (T *)(uintptr_t)((unsigned long long)uni(w[0]) | ((unsigned long long)uni(w[1]) << 32));
+}
+// layer i of policy `pol` from the policy table (td7f_lin is 14 words)
+__device__ __forceinline__ Lin lin_at(const td7f_lin *tab, int pol, int i) {
+    static_assert(sizeof(td7f_lin) == 56, "td7f_lin: 3 pointers, 4 ints, pointer, int64");
+    const uint32_t *p = (const uint32_t *)(tab + (size_t)pol * 7 + i);
+    uint32_t w[14];
+#pragma unroll
+    for (int k = 0; k < 14; ++k) w[k] = ldg(p + k);
+    Lin L;
+    L.wf = uni_ptr<const u32x4>(w);
+    L.wb = uni_ptr<const u32x4>(w + 2);
+    L.b = uni_ptr<const float>(w + 4);
+    L.N = (int)uni(w[6]);
+    L.K = (int)uni(w[7]);
+    L.ksf = (int)uni(w[8]);
+    L.ksb = (int)uni(w[9]);
+    L.w = uni_ptr<const float>(w + 10);
+    L.ldw = (long)((unsigned long long)uni(w[12]) | ((unsigned long long)uni(w[13]) << 32));
+    return L;
+}
+
+// select_kernel<P, TH, 1, 0> on the tile (policy, row0, row_end) of blockIdx.x.
+template <int P, int TH>
+__global__ __launch_bounds__(NTH) void select_multi_kernel(SelectMultiArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int rows = TR;
+    const int *tp = a.tiles + 3 * (size_t)blockIdx.x;
+    const int pol = (int)uni((uint32_t)ldg(tp)), row0 = (int)uni((uint32_t)ldg(tp + 1)),
+              rend = (int)uni((uint32_t)ldg(tp + 2));
+    int si = 0;
+    FSTAMP(si);
+    const Lin zs1 = lin_at(a.pol, pol, 0), l3 = lin_at(a.pol, pol, 6);
+    RowStage so;
+    ThinStage<THIN_NC> tw;
+    row_issue(so, a.obs, a.S, a.S, row0, rend);
+    thin_issue(tw, l3.w, l3.ldw, 0, false, a.A, l3.K);
+    Ring<TH> R;
+    ring_fill<TH>(R, GDesc{zs1.wf, zs1.ksf, 0});
+    zero_lds(lds, a.lds_bytes);
+    __syncthreads();
+    row_put16<P>(lds, so, a.X, 0, a.S, row0, rend);
+    thin_put<P>(lds, tw, a.TW, a.A, l3.K);
+    __syncthreads();
+    // zs = fixed_encoder.zs(obs) (:93-97) -> CAT[:, Ha:Ha+Z]
+    const Lin zs2 = lin_at(a.pol, pol, 1), zs3 = lin_at(a.pol, pol, 2), l0 = lin_at(a.pol, pol, 3);
+    layer_fwd<P, 1, TH>(lds, R, a.X, zs1, &zs2, a.act_enc, a.H1, 0, NO32, nullptr, 0, row0, rend, si);
+    layer_fwd<P, 1, TH>(lds, R, a.H1, zs2, &zs3, a.act_enc, a.H2, 0, NO32, nullptr, 0, row0, rend, si);
+    layer_fwd<P, 1, TH>(lds, R, a.H2, zs3, &l0, ACT_NONE, NO16, 0, a.F, nullptr, 0, row0, rend, si);
+    norm_fwd<P>(lds, a.F, a.Z, rows, 1e-8f, a.CAT, a.Ha, NO16, 0, NO32, nullptr, 0, nullptr, nullptr, row0, rend);
+    __syncthreads();
+    // actor (:72-77): AvgL1Norm(l0(s)) | zs -> l1 -> l2 -> tanh(l3)
+    const Lin l1 = lin_at(a.pol, pol, 4), l2 = lin_at(a.pol, pol, 5);
+    layer_fwd<P, 1, TH>(lds, R, a.X, l0, &l1, ACT_NONE, NO16, 0, a.F, nullptr, 0, row0, rend, si);
+    norm_fwd<P>(lds, a.F, a.Ha, rows, 1e-8f, a.CAT, 0, NO16, 0, NO32, nullptr, 0, nullptr, nullptr, row0, rend);
+    __syncthreads();
+    // F overlaid H1 | H2: their zero padding columns restored (see select_kernel)
+    if (a.F.off == a.H1.off) {
+        zero_lds(lds + a.H1.off, a.H2.off + rows * a.H2.ld * 2 - a.H1.off);
+        __syncthreads();
+    }
+    layer_fwd<P, 1, TH>(lds, R, a.CAT, l1, &l2, a.act_actor, a.H1, 0, NO32, nullptr, 0, row0, rend, si);
+    layer_fwd<P, 1, TH>(lds, R, a.H1, l2, (const Lin *)nullptr, a.act_actor, a.H2, 0, NO32, nullptr, 0, row0, rend, si);
+    layer_thin_fwd<P, THIN_NC>(lds, a.H2, l3, a.TW, ACT_TANH, a.FT, rows, nullptr, 0, row0, rend, si);
+    if (a.noisy) {
+        // one noise state for the launch: the Philox element is the global
+        // row's, the last workgroup out takes the ticket
+        noise_rows<P>(lds, a.FT, a.A, rows, row0, rend, a.nz, a.out, NO16, 0, NO16, 0, true);
+        return;
+    }
+    for (int k = threadIdx.x; k < rows * a.A; k += NTH) {
+        const int row = k / a.A, c = k - row * a.A;
+        if (row0 + row < rend)
+            stg(a.out + (size_t)(row0 + row) * a.A + c, fminf(fmaxf(*p32(lds, a.FT, row, c), -1.0f), 1.0f) * a.scale);
+    }
+}
+
+}  // namespace td7f
+
+using namespace td7f;
+
+extern "C" {
+
+int td7f_multi_tiles(int32_t npol, const int32_t *seg, int32_t *tiles, int32_t cap) {
+    if (npol <= 0 || !seg || seg[0] != 0 || cap < 0) return EXO_EINVAL;
+    long nt = 0;
+    for (int p = 0; p < npol; ++p) {
+        if (seg[p + 1] < seg[p]) return EXO_EINVAL;
+        for (int r = seg[p]; r < seg[p + 1]; r += TR, ++nt)
+            if (tiles && nt < cap) {
+                tiles[3 * nt] = p;
+                tiles[3 * nt + 1] = r;
+                tiles[3 * nt + 2] = std::min(r + TR, seg[p + 1]);
+            }
+    }
+    if (nt > INT32_MAX) return EXO_ERANGE;
+    return (int)nt;
+}
+
+// The host image of the policy table from the same enc / actor arrays the
+// launch validates: the one place that fixes lin_at's layout on the host side.
+int td7f_multi_policy_table(int32_t npol, const td7f_lin *enc, const td7f_lin *actor, td7f_lin *table) {
+    if (npol <= 0 || !enc || !actor || !table) return EXO_EINVAL;
+    for (int p = 0; p < npol; ++p) {
+        for (int i = 0; i < 3; ++i) table[7 * (size_t)p + i] = enc[3 * (size_t)p + i];
+        for (int i = 0; i < 4; ++i) table[7 * (size_t)p + 3 + i] = actor[4 * (size_t)p + i];
+    }
+    return EXO_OK;
+}
+
+int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
+                      const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
+                      const float *obs, int32_t n, const td7f_noise *noise, float *out, float scale, void *stream) {
+    const bool prec_ok = prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_F32;
+    if (!prec_ok || !act || npol <= 0 || !enc || !actor || !policies_dev || !seg || !tiles_dev || !obs || !out ||
+        n <= 0)
+        return EXO_EINVAL;
+    if (seg[0] != 0 || seg[npol] != n) return EXO_EINVAL;
+    long nt = 0;
+    for (int p = 0; p < npol; ++p) {
+        if (seg[p + 1] < seg[p]) return EXO_EINVAL;
+        nt += (seg[p + 1] - seg[p] + TR - 1) / TR;
+    }
+    if (nt != ntiles) return EXO_EINVAL;
+    const int kd = kd_of(prec);
+    int th = 0;
+    for (int p = 0; p < npol; ++p) {
+        const td7f_lin *e = enc + 3 * (size_t)p, *c = actor + 4 * (size_t)p;
+        td7f_lin all[7] = {e[0], e[1], e[2], c[0], c[1], c[2], c[3]};
+        const int t = th_of(all, 7);
+        if ((t != 4 && t != 5) || (p && t != th)) return EXO_EINVAL;
+        th = t;
+        // one LDS plan: every policy has policy 0's shape
+        const td7f_lin *e0 = enc, *c0 = actor;
+        for (int i = 0; i < 7; ++i) {
+            const td7f_lin &x = i < 3 ? e[i] : c[i - 3], &y = i < 3 ? e0[i] : c0[i - 3];
+            if (x.n_out != y.n_out || x.n_in != y.n_in || x.ksf != y.ksf) return EXO_EINVAL;
+        }
+    }
+    SelectMultiArgs a{};
+    a.pol = (const td7f_lin *)policies_dev;
+    a.tiles = tiles_dev;
+    a.act_enc = act[0];
+    a.act_actor = act[1];
+    a.obs = obs;
+    a.S = enc[0].n_in;
+    a.A = actor[3].n_out;
+    a.Z = enc[2].n_out;
+    a.Ha = actor[0].n_out;
+    if (actor[0].n_in != a.S || actor[1].n_in != a.Ha + a.Z || a.A > THIN_NC || a.S > NTH) return EXO_EINVAL;
+    if ((long)n * a.A >= (1L << 31)) return EXO_ERANGE;  // the Philox element index is 32 bits
+    a.out = out;
+    a.noisy = noise != nullptr;
+    if (noise) a.nz = noise_of(*noise);
+    a.scale = scale;
+    // select_impl's plan at RT = 1
+    const int rows = TR, hmax = std::max(enc[0].n_out, std::max(enc[1].n_out, std::max(a.Ha, actor[1].n_out)));
+    Bump b;
+    a.X = b.r16(rows, ld16(a.S, kd));
+    a.H1 = b.r16(rows, ld16(hmax, kd));
+    a.H2 = b.r16(rows, ld16(hmax, kd));
+    const int fld = std::max(std::max(a.Z, a.Ha), 16);
+    if (rows * fld * 4 <= a.H2.off + rows * a.H2.ld * 2 - a.H1.off) {
+        a.F = R32{a.H1.off, fld};  // overlays H1 | H2 (both dead whenever F is written)
+    } else {
+        a.F = b.r32(rows, fld);
+    }
+    a.CAT = b.r16(rows, ld16(a.Ha + a.Z, kd));
+    a.TW = b.r32(THIN_NC, actor[3].n_in);
+    a.FT = b.r32(rows, 16);
+    a.lds_bytes = b.off;
+    return DISPATCH(prec, th, select_multi_kernel, dim3((unsigned)ntiles), b.off, a, (hipStream_t)stream);
+}
+
+}  // extern "C"

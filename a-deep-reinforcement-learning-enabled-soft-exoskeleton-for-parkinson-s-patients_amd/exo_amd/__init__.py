@@ -21,4 +21,8 @@ def __getattr__(name):
     if name == "OfflineTrainer":
         from .rollout import OfflineTrainer
         return OfflineTrainer
+    # the batched policy evaluation (exo_amd.evaluate), on first use as well
+    if name == "Evaluator":
+        from .evaluate import Evaluator
+        return Evaluator
     raise AttributeError(f"module 'exo_amd' has no attribute {name!r}")

@@ -111,6 +111,7 @@ EXPORTS = {
     "exo_get_state_host": (c_int32, [c_void_p, c_int32, P(c_double)]),
     "exo_set_state_host": (c_int32, [c_void_p, c_int32, P(c_double)]),
     "exo_set_seed": (c_int32, [c_void_p, c_uint64]),
+    "exo_restart": (c_int32, [c_void_p, c_uint64, c_void_p]),
     "exo_set_step_variant": (c_int32, [c_void_p, c_int32]),
     "exo_set_step_budget": (c_int32, [c_void_p, c_int32]),
     "exo_step_carry": (c_int32, [c_void_p] * 9),
@@ -236,6 +237,11 @@ EXPORTS = {
                               c_int32, c_int32, c_void_p]),
     "td7f_select_part": (c_int32, [c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), c_void_p, c_int32, P(TD7FNoise),
                                    c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "td7f_select_multi": (c_int32, [c_int32, P(c_int32), c_int32, P(TD7FLin), P(TD7FLin), c_void_p, P(c_int32),
+                                    c_void_p, c_int32, c_void_p, c_int32, P(TD7FNoise), c_void_p, ctypes.c_float,
+                                    c_void_p]),
+    "td7f_multi_tiles": (c_int32, [c_int32, P(c_int32), P(c_int32), c_int32]),
+    "td7f_multi_policy_table": (c_int32, [c_int32, P(TD7FLin), P(TD7FLin), P(TD7FLin)]),
     "td7f_target": (c_int32, [c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), P(TD7FLin), c_void_p, c_int32,
                               P(TD7FNoise), c_void_p, c_void_p, c_void_p]),
     "td7f_fixed": (c_int32, [c_int32, P(c_int32), P(TD7FLin), c_void_p, c_void_p, c_int32, c_void_p, c_void_p,

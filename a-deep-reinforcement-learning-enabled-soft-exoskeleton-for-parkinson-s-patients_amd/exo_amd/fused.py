@@ -14,6 +14,7 @@ launch wrappers; TD7Learner routes its passes here when `fused` is on.
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -635,3 +636,172 @@ class FusedTrain:
 
     def wgrad_actor(self, adam=False):
         self._wgrad(self.jobs_a, self.adam_a, self.L.actor_optimizer, adam)
+
+
+# ------------------------------------------------------------------ many policies, one launch
+def multi_tiles(seg, rows=16):
+    """The tile table of td7f_select_multi (include/exo_amd.h): policy p owns
+    the rows [seg[p], seg[p+1]); each segment is cut into ceil(len / rows)
+    tiles from its first row, the last one ragged, so no tile straddles two
+    segments.  seg: non-decreasing integers, seg[0] == 0.  Returns int32
+    [ntiles, 3] = (policy, row0, row_end); empty segments give no tiles."""
+    s = np.asarray(seg)
+    if s.ndim != 1 or s.size < 2 or not np.issubdtype(s.dtype, np.integer):
+        raise ValueError("multi_tiles: seg must be a 1-D integer array of npol + 1 entries")
+    s = s.astype(np.int64)
+    if s[0] != 0 or np.any(np.diff(s) < 0) or s[-1] >= 2 ** 31 or int(rows) <= 0:
+        raise ValueError("multi_tiles: seg must start at 0, not decrease and stay below 2^31")
+    rows = int(rows)
+    cnt = -(-np.diff(s) // rows)
+    pol = np.repeat(np.arange(s.size - 1, dtype=np.int64), cnt)
+    first = np.cumsum(cnt) - cnt  # index of each policy's first tile
+    row0 = s[:-1][pol] + (np.arange(pol.size, dtype=np.int64) - first[pol]) * rows
+    return np.stack([pol, row0, np.minimum(row0 + rows, s[1:][pol])], axis=1).astype(np.int32).reshape(-1, 3)
+
+
+def select_multi_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, noise, out, scale,
+                     npol=None):
+    """td7f_select_multi as it stands in the C ABI; returns its status code.
+    enc / actor: TD7FLin arrays of 3 / 4 entries per policy; seg: a python
+    sequence of npol + 1 ints; noise: a TD7FNoise or None (deterministic)."""
+    npol = len(seg) - 1 if npol is None else npol
+    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
+    return nat.lib().td7f_select_multi(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg, nat.ptr(tiles_dev),
+                                       int(ntiles), nat.ptr(obs), int(n),
+                                       ctypes.byref(noise) if noise is not None else None, nat.ptr(out),
+                                       float(scale), nat.stream_ptr(obs.device))
+
+
+class PolicySet:
+    """K policies -- (actor, fixed encoder) module pairs of one shape -- packed
+    for td7f_select_multi: one launch in which policy p acts on the rows
+    [seg[p], seg[p+1]) of the observations (TD7_multi_agent.py:192-209 /
+    TD7_multi_agent_Pink_noise.py:212-214 per policy).  The set owns packed
+    forward-only copies of the modules' weights (PackedNet) and the device
+    policy table (pointers and shapes: refresh() repacks in place and keeps
+    it); it reads the modules and changes nothing of theirs."""
+
+    def __init__(self, policies, precision, device, activations=None):
+        from .td7 import Hyperparameters
+        if precision not in PREC:
+            raise ValueError(f"PolicySet: precision must be one of {sorted(PREC)}")
+        policies = list(policies)
+        if not policies:
+            raise ValueError("PolicySet: no policies")
+        self.prec = PREC[precision]
+        self.precision = precision
+        self.dev = nat.require_gpu(device)
+        if activations is None:
+            hp = Hyperparameters()
+            activations = (hp.enc_activ, hp.actor_activ)
+        codes = [ops.act_code(f) for f in activations]
+        if any(c is None or c == ops.ACT_CODES["tanh"] for c in codes):
+            raise ValueError("PolicySet: activations must be relu or elu")
+        self.act_codes = (ctypes.c_int32 * 3)(codes[0], codes[1], 0)
+        self.policies = policies
+        self.nets = []
+        for actor, enc in policies:
+            layers = encoder_layers(enc)[:3] + actor_layers(actor)
+            if any(w.device != self.dev or w.dtype != torch.float32 for w, _ in layers):
+                raise ValueError(f"PolicySet: the modules must hold fp32 weights on {self.dev}")
+            self.nets.append(PackedNet(layers, self.prec))
+        shape0 = [(pl.N, pl.K) for pl in self.nets[0].layers]
+        for k, net in enumerate(self.nets):
+            if [(pl.N, pl.K) for pl in net.layers] != shape0:
+                raise ValueError(f"PolicySet: policy {k} has another shape than policy 0 (one LDS plan serves the launch)")
+        self.S, self.A = self.nets[0].layers[0].K, self.nets[0].layers[6].N
+        self.enc = _lin_array([pl for net in self.nets for pl in net.layers[:3]])
+        self.actor = _lin_array([pl for net in self.nets for pl in net.layers[3:]])
+        # the device policy table, td7f_lin [K][7], from the arrays the launch validates
+        host = (TD7FLin * (7 * len(self.nets)))()
+        nat.check(nat.lib().td7f_multi_policy_table(len(self.nets), self.enc, self.actor, host),
+                  "td7f_multi_policy_table")
+        self.table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.dev)
+        self._tiles = {}
+        self.pack()
+        self._probe()
+
+    @classmethod
+    def from_agents(cls, agents, use_checkpoint=True, precision=None, device=None):
+        """The agents' checkpoint policies (checkpoint_actor / checkpoint_encoder:
+        what TD7 reports) or, use_checkpoint=False, their live ones (actor /
+        fixed_encoder)."""
+        agents = list(agents)
+        L0 = agents[0].learner
+        pairs = [(a.learner.checkpoint_actor, a.learner.checkpoint_encoder) if use_checkpoint
+                 else (a.learner.actor, a.learner.fixed_encoder) for a in agents]
+        return cls(pairs, precision or L0.precision, device or L0.device, (L0.hp.enc_activ, L0.hp.actor_activ))
+
+    def __len__(self):
+        return len(self.nets)
+
+    def _probe(self):
+        """the launch's arguments and LDS plan checked once (td7f_probe)"""
+        n = 16 * len(self)
+        seg = [16 * k for k in range(len(self) + 1)]
+        obs = torch.zeros((n, self.S), dtype=torch.float32, device=self.dev)
+        lib = nat.lib()
+        lib.td7f_probe(1)
+        try:
+            try:
+                self.act(obs, seg)
+            except RuntimeError as e:
+                raise PlanError(f"td7f_select_multi cannot run this policy shape: {e}") from e
+        finally:
+            lib.td7f_probe(0)
+
+    def pack(self, k=None):
+        """td7f_pack of policy k's (None: every policy's) weights, TD7F_MAX_PACK jobs per launch."""
+        nets = self.nets if k is None else [self.nets[k]]
+        jobs = [pl.job() for net in nets for pl in net.layers]
+        st = nat.stream_ptr(self.dev)
+        for i in range(0, len(jobs), MAX_PACK):
+            part = jobs[i:i + MAX_PACK]
+            nat.check(nat.lib().td7f_pack(self.prec, len(part), (TD7FPackJob * len(part))(*part), st), "td7f_pack")
+        for net in nets:
+            net._ver = net._versions()
+
+    def refresh(self, k=None):
+        """Repack policy k (None: every policy) when its master weights changed
+        through torch since its last pack (version counters, PackedNet.refresh);
+        weights written by a HIP kernel need pack()."""
+        ks = range(len(self)) if k is None else [k]
+        for j in ks:
+            if self.nets[j]._versions() != self.nets[j]._ver:
+                self.pack(j)
+
+    def tiles(self, seg):
+        """(seg as a tuple, device tile table, ntiles) for seg; built once per
+        seg -- a new one needs an allocation and a copy, so not inside a capture."""
+        key = tuple(int(v) for v in seg)
+        hit = self._tiles.get(key)
+        if hit is None:
+            if len(key) != len(self) + 1:
+                raise ValueError(f"PolicySet: seg needs {len(self) + 1} entries")
+            if self.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("PolicySet.act: call once eagerly with this seg before graph capture")
+            t = multi_tiles(np.asarray(key, dtype=np.int64))
+            # (an empty table still needs an address)
+            dev = torch.as_tensor(t if len(t) else np.zeros((1, 3), np.int32)).to(self.dev)
+            hit = self._tiles[key] = (dev, len(t))
+        return key, hit[0], hit[1]
+
+    @torch.no_grad()
+    def act(self, obs, seg, out=None, scale=1.0, noise=None):
+        """One td7f_select_multi launch: out[r] = policy p's action for obs[r],
+        seg[p] <= r < seg[p+1].  noise None: deterministic, clamp(tanh(.), -1,
+        1) * scale, no noise state touched; a TD7FNoise (FusedNets._noise):
+        that one exploration-noise state for the whole launch (its own scale
+        applies).  Repack changed weights with refresh() first."""
+        key, tiles, nt = self.tiles(seg)
+        obs = obs.contiguous()
+        n = obs.shape[0]
+        if obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != self.S:
+            raise ValueError(f"PolicySet.act: obs must be float32 [n, {self.S}]")
+        if out is None:
+            out = torch.empty((n, self.A), dtype=torch.float32, device=obs.device)
+        elif tuple(out.shape) != (n, self.A) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError(f"PolicySet.act: out must be contiguous float32 {(n, self.A)}")
+        nat.check(select_multi_raw(self.prec, self.act_codes, self.enc, self.actor, self.table, key, tiles, nt, obs,
+                                   n, noise, out, scale), "td7f_select_multi")
+        return out

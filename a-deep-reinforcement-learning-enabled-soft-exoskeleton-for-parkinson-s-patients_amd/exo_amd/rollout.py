@@ -1763,6 +1763,35 @@ class OfflineTrainer:
         for _ in range(int(n)):
             self.step()
 
+    def evaluate(self, n_envs=64, use_checkpoint=False, **env):
+        """The policy this trainer trains -- the live actor with the fixed
+        encoder, what an offline run reports (the reference's offline runs use
+        use_checkpoints=False) -- for one deterministic episode in n_envs envs
+        (exo_amd.Evaluator, built on first use and kept for the same
+        arguments); env: Evaluator.from_agent's keyword arguments.  The
+        weights are repacked from the nets at every call, so the result follows
+        the training steps taken so far.  use_checkpoint=True evaluates
+        checkpoint_actor / checkpoint_encoder instead: only the online episode
+        schedule (Agent.maybe_train_and_checkpoint) or Agent.load writes those,
+        step() never does.  Returns that policy's result dict; touches neither
+        the agent's nor this trainer's state.  close() frees the evaluator."""
+        from .evaluate import Evaluator
+        key = (int(n_envs), bool(use_checkpoint),
+               tuple((k, np.asarray(v).shape, np.asarray(v).tobytes()) for k, v in sorted(env.items())))
+        if getattr(self, "_evaluator_key", None) != key:
+            self.close()
+            self._evaluator = Evaluator.from_agent(self.agent, n_envs, use_checkpoint=use_checkpoint, **env)
+            self._evaluator_key = key
+        return self._evaluator.evaluate()[0]
+
+    def close(self):
+        """Free evaluate()'s evaluator (its env context, packed weights and step graph)."""
+        ev, self._evaluator, self._evaluator_key = getattr(self, "_evaluator", None), None, None
+        if ev is not None:
+            ev.close()
+
     def release_graphs(self):
-        """retire_graphs(self): destroy the captured graphs (synchronises)."""
+        """retire_graphs(self): destroy the captured graphs (synchronises);
+        evaluate()'s evaluator is closed with them."""
+        self.close()
         return retire_graphs(self)

@@ -263,6 +263,16 @@ class VecExoskeletonEnv:
         nat.check(nat.lib().exo_set_tremor_model(self._ctx, None if j is None else j.ctypes.data_as(nat.P(ctypes.c_double)),
                                                  self.TREMOR_SIGN[sign]), "exo_set_tremor_model", self._ctx)
 
+    def restart(self, seed):
+        """Back to where VecExoskeletonEnv(n, seed=seed, ...) starts
+        (exo_restart): the state a reset carries over from the episode before
+        it (arm pose, reference, previous actions) cleared, the draw key's
+        episode index rewound, the constructor's reset run again -- the next
+        reset() is a fresh env's first, so an evaluation can be repeated on
+        the same episodes.  Ideal physics only."""
+        nat.check(nat.lib().exo_restart(self._ctx, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), self._stream()),
+                  "exo_restart", self._ctx)
+
     def set_step_clock(self, on=True):
         """Step clock (include/exo_amd.h exo_set_step_clock): every later step
         launch -- eager or inside a captured graph -- is bracketed by device

@@ -220,6 +220,16 @@ int exo_set_multibody_state_host(exo_ctx *ctx, int32_t env, const double *q19, c
 
 /* Re-key the Philox draw streams of later resets (ExoskeletonEnv_train.seed, :189-191). */
 int exo_set_seed(exo_ctx *ctx, uint64_t seed);
+/* Put the context back where exo_create(..., seed, ...) leaves it, on `stream`:
+ * a reset carries the arm pose, the reference and the previous actions over
+ * from the episode before it (Exoskeleton_env.py:193-254 resets none of them)
+ * and draws under the key (seed, env, episode), so a repeated evaluation on
+ * the same episodes needs all of that rewound, not only the seed.  Clears the
+ * carried state and the episode indices, sets the seed and runs the
+ * constructor's initialize_movement (episode 0); the caller's next exo_reset
+ * is then a fresh context's first.  Ideal physics only (EXO_EINVAL otherwise);
+ * configuration, motions, step variant and tremor model are kept. */
+int exo_restart(exo_ctx *ctx, uint64_t seed, void *stream);
 
 const char *exo_last_error(const exo_ctx *ctx);
 void exo_destroy(exo_ctx *ctx);
@@ -721,6 +731,56 @@ int td7f_select(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
 int td7f_select_part(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor,
                      const float *obs_dev, int32_t n, const td7f_noise *noise, float *act_out_dev, int32_t wg_cap,
                      int32_t rt, void *zs_img_dev, int32_t mode, void *stream);
+/* select_action of npol policies in one launch (csrc/td7_fused_multi.hip;
+ * TD7_multi_agent.py:192-209 / TD7_multi_agent_Pink_noise.py:212-214 per
+ * policy): policy p -- fixed encoder zs1..zs3 at enc[3p..3p+2], actor l0..l3
+ * at actor[4p..4p+3] -- acts on the contiguous rows [seg[p], seg[p+1]) of
+ * obs_dev [n][S]; actions to act_out_dev [n][A].  seg is a host array of
+ * npol + 1 entries, non-decreasing, seg[0] = 0, seg[npol] = n; empty segments
+ * are allowed.  All policies share one shape (every n_in, n_out and ksf equal
+ * layer by layer) and td7f_select's limits hold; 16-row tiles at every
+ * precision.  EXO_EINVAL otherwise, nothing launched.
+ *
+ * The launch reads two device tables, built by the caller outside the launch
+ * (the call itself allocates nothing and copies nothing to the device, so it
+ * can be captured in a graph):
+ *   policies_dev  td7f_lin [npol][7] -- for each policy zs1, zs2, zs3, l0, l1,
+ *                 l2, l3, a byte copy of the host structs given in enc /
+ *                 actor.  It holds pointers and shapes only: td7f_pack of a
+ *                 policy's weights in place keeps it valid.
+ *   tiles_dev     int32 [ntiles][3] = (policy, row0, row_end), one row per
+ *                 workgroup: segment p of len rows is cut into ceil(len / 16)
+ *                 tiles from seg[p], the last one ragged (row_end = seg[p+1]),
+ *                 so no tile straddles two segments; rows >= row_end are
+ *                 neither read nor written.  td7f_multi_tiles writes this
+ *                 table on the host; it changes only when seg does.  ntiles
+ *                 must equal the count td7f_multi_tiles returns for seg.
+ * The two tables must describe the same enc / actor / seg the call is given:
+ * the host validates its own arguments, it cannot read the tables.
+ *
+ * noise == NULL: deterministic, act_out = clamp(tanh(...), -1, 1) * scale; no
+ * noise state is read or written.  noise != NULL: td7f_select's exploration
+ * noise with that one noise state for the whole launch (Philox element =
+ * global row * A + column, so npol = 1 equals td7f_select at rt = 1 bit for
+ * bit; sigma and the call counter advance once, by the last workgroup out);
+ * `scale` is then unused (noise->scale applies).  A sigma per policy is out of
+ * scope: one td7f_noise serves the launch. */
+int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
+                      const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
+                      const float *obs_dev, int32_t n, const td7f_noise *noise, float *act_out_dev, float scale,
+                      void *stream);
+/* The tile table of td7f_select_multi for seg (host, npol + 1 entries) into
+ * tiles [cap][3] (host; NULL: count only).  Returns the number of tiles
+ * (sum of ceil(len / 16); at most cap rows are written) or EXO_EINVAL for
+ * npol <= 0, seg[0] != 0 or a decreasing seg. */
+int td7f_multi_tiles(int32_t npol, const int32_t *seg, int32_t *tiles, int32_t cap);
+/* The host image of td7f_select_multi's policy table, table [npol][7] (host),
+ * from the enc [npol][3] / actor [npol][4] arrays the launch is given; the
+ * caller copies it to the device once (npol * 7 * sizeof(td7f_lin) bytes).
+ * Build the table with this call from the very arrays passed to
+ * td7f_select_multi, so that what the host validates is what the kernel
+ * reads. */
+int td7f_multi_policy_table(int32_t npol, const td7f_lin *enc, const td7f_lin *actor, td7f_lin *table);
 /* The critic target chain (TD7_multi_agent.py:233-241): fixed_target_zs(s'),
  * next_action = actor_target(s', zs) + clipped noise, fixed_target_zsa and both
  * heads of critic_target -> qt_dev [B][2].  tenc: zs1..zs3, zsa1..zsa3;

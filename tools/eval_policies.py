@@ -87,6 +87,44 @@ def evaluate(cfg, path, episodes, physics, seed, device):
     return r
 
 
+def evaluate_batched(cfgs, paths, episodes, physics, seed, device, precision="fp32"):
+    """Every configuration in one exo_amd.Evaluator: one env of len(cfgs) x 8 x
+    episodes envs, configuration k on its own segment with its own tremor
+    sequence, one td7f_select_multi launch per step.  The same dicts as
+    evaluate(); env e of a segment is env (segment start + e) of the batch, so
+    the draws of all but the first configuration differ from the sequential
+    path's (there every configuration's envs are 0 .. 8 x episodes - 1)."""
+    from exo_amd import Evaluator
+    from exo_amd.fused import PolicySet
+    hp = Hyperparameters(actor_hdim=300)
+    n = 8 * episodes
+    t0 = time.time()
+    ps = PolicySet([policy(p, device) for p in paths], precision, device, activations=(hp.enc_activ, hp.actor_activ))
+    seqs = [[int(c) for c in cfg.strip("[]").split(",")] + [0, 0, 0] for cfg in cfgs]
+    ev = Evaluator(ps, [n] * len(cfgs), env_kwargs=EVAL_ENV, per_policy_env_kwargs=[dict(tremor_sequence=s) for s in seqs],
+                   seed=seed, physics=physics)
+    out = []
+    try:
+        for cfg, r in zip(cfgs, ev.evaluate(episodes=episodes)):
+            r = dict(cfg=cfg, episodes=episodes, envs=n, physics=physics, total=r["total"], occurrence=r["occurrence"],
+                     torque_any=r["torque_any"], torque_all=r["torque_all"], env_steps=r["env_steps"])
+            r["anchor"] = dict(zip(("total", "occurrence", "torque_any"), ANCHORS[cfg]))
+            out.append(r)
+    finally:
+        ev.close()
+    for r in out:
+        r["seconds"] = (time.time() - t0) / len(out)  # the batch's time, shared
+    return out
+
+
+def show(r):
+    an = r["anchor"]
+    print(f"{r['cfg']:10s} {r['total'][0]:8.2f}+-{r['total'][1]:5.2f} {an['total']:8.2f} "
+          f"{r['occurrence'][0]:7.2f}+-{r['occurrence'][1]:5.2f} {an['occurrence']:8.2f} "
+          f"{r['torque_any'][0]:7.2f}+-{r['torque_any'][1]:5.2f} {an['torque_any']:8.2f}  {r['seconds']:.1f}",
+          flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--episodes", type=int, default=100)
@@ -94,23 +132,26 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dir", default=os.path.join(REPO, "policies"))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--batched", action="store_true",
+                    help="all configurations as one env batch through exo_amd.Evaluator (td7f_select_multi)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     res = []
     print(f"{'cfg':10s} {'total %':>16s} {'anchor':>8s} {'occur %':>15s} {'anchor':>8s} {'torque any %':>15s} {'anchor':>8s}  s")
-    for f in sorted(os.listdir(a.dir)):
-        if not f.endswith(".safetensors"):
-            continue
+    files = [f for f in sorted(os.listdir(a.dir)) if f.endswith(".safetensors")]
+    if a.batched:
+        cfgs = [f[:-len(".safetensors")] for f in files]
+        res = evaluate_batched(cfgs, [os.path.join(a.dir, f) for f in files], a.episodes, a.physics, a.seed, dev)
+        for r in res:
+            show(r)
+        files = []
+    for f in files:
         cfg = f[:-len(".safetensors")]
         t0 = time.time()
         r = evaluate(cfg, os.path.join(a.dir, f), a.episodes, a.physics, a.seed, dev)
         r["seconds"] = time.time() - t0
         res.append(r)
-        an = r["anchor"]
-        print(f"{cfg:10s} {r['total'][0]:8.2f}+-{r['total'][1]:5.2f} {an['total']:8.2f} "
-              f"{r['occurrence'][0]:7.2f}+-{r['occurrence'][1]:5.2f} {an['occurrence']:8.2f} "
-              f"{r['torque_any'][0]:7.2f}+-{r['torque_any'][1]:5.2f} {an['torque_any']:8.2f}  {r['seconds']:.1f}",
-              flush=True)
+        show(r)
     if a.out:
         with open(a.out, "w") as fh:
             json.dump(res, fh, indent=1)
