@@ -25,6 +25,22 @@
 // Both tables are read with wave-uniform (scalar) loads: the addresses depend
 // on blockIdx.x alone and nothing in the kernel stores to global memory before
 // its last stage.
+//
+//   td7f_select_multi_noise : the same launch with one exploration-noise state
+//                       PER POLICY (sigma, clip, decay, Philox stream), for
+//                       collecting data from many behaviour policies at once:
+//
+//   noise table  td7f_noise_row [npol] in device memory: key, pointers to the
+//                policy's call counter and sigma, sigma_dec, clip.  The
+//                immutable fields are read wave-uniform like the other tables;
+//                *sigma and *counter, which the launch writes, with ordinary
+//                loads (noise_rows).
+//   seg          int32 [npol + 1], a device copy: the Philox element of row r
+//                of policy p is (r - seg[p]) * A + c, so what a policy draws
+//                depends neither on its neighbours nor on where its segment
+//                starts -- its rows equal its own td7f_select, noise included.
+//   ticket       one word for the launch: the last workgroup out advances
+//                every policy with a non-empty segment (thread k policy k).
 #include "td7_fused.h"
 
 #include <algorithm>
@@ -73,14 +89,19 @@ __device__ __forceinline__ Lin lin_at(const td7f_lin *tab, int pol, int i) {
     return L;
 }
 
-// select_kernel<P, TH, 1, 0> on the tile (policy, row0, row_end) of blockIdx.x.
+// the tile (policy, row0, row_end) of blockIdx.x
+__device__ __forceinline__ void tile_at(const int *tiles, int &pol, int &row0, int &rend) {
+    const int *tp = tiles + 3 * (size_t)blockIdx.x;
+    pol = (int)uni((uint32_t)ldg(tp));
+    row0 = (int)uni((uint32_t)ldg(tp + 1));
+    rend = (int)uni((uint32_t)ldg(tp + 2));
+}
+
+// select_kernel<P, TH, 1, 0>'s networks on the tile (pol, row0, rend): leaves
+// tanh(l3(...)) of the tile's rows in the fp32 region a.FT.
 template <int P, int TH>
-__global__ __launch_bounds__(NTH) void select_multi_kernel(SelectMultiArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char lds[];
+__device__ __forceinline__ void select_multi_rows(char *lds, const SelectMultiArgs &a, int pol, int row0, int rend) {
     constexpr int rows = TR;
-    const int *tp = a.tiles + 3 * (size_t)blockIdx.x;
-    const int pol = (int)uni((uint32_t)ldg(tp)), row0 = (int)uni((uint32_t)ldg(tp + 1)),
-              rend = (int)uni((uint32_t)ldg(tp + 2));
     int si = 0;
     FSTAMP(si);
     const Lin zs1 = lin_at(a.pol, pol, 0), l3 = lin_at(a.pol, pol, 6);
@@ -115,6 +136,16 @@ __global__ __launch_bounds__(NTH) void select_multi_kernel(SelectMultiArgs a) {
     layer_fwd<P, 1, TH>(lds, R, a.CAT, l1, &l2, a.act_actor, a.H1, 0, NO32, nullptr, 0, row0, rend, si);
     layer_fwd<P, 1, TH>(lds, R, a.H1, l2, (const Lin *)nullptr, a.act_actor, a.H2, 0, NO32, nullptr, 0, row0, rend, si);
     layer_thin_fwd<P, THIN_NC>(lds, a.H2, l3, a.TW, ACT_TANH, a.FT, rows, nullptr, 0, row0, rend, si);
+}
+
+// select_kernel<P, TH, 1, 0> on the tile (policy, row0, row_end) of blockIdx.x.
+template <int P, int TH>
+__global__ __launch_bounds__(NTH) void select_multi_kernel(SelectMultiArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int rows = TR;
+    int pol, row0, rend;
+    tile_at(a.tiles, pol, row0, rend);
+    select_multi_rows<P, TH>(lds, a, pol, row0, rend);
     if (a.noisy) {
         // one noise state for the launch: the Philox element is the global
         // row's, the last workgroup out takes the ticket
@@ -126,6 +157,77 @@ __global__ __launch_bounds__(NTH) void select_multi_kernel(SelectMultiArgs a) {
         if (row0 + row < rend)
             stg(a.out + (size_t)(row0 + row) * a.A + c, fminf(fmaxf(*p32(lds, a.FT, row, c), -1.0f), 1.0f) * a.scale);
     }
+}
+
+// ---- one noise state per policy (td7f_select_multi_noise)
+struct SelectMultiNoiseArgs {
+    SelectMultiArgs s;          // s.nz / s.noisy unused
+    const td7f_noise_row *nzt;  // device [npol]
+    const int *seg;             // device [npol + 1]
+    uint32_t *ticket;
+    const float *z;  // given standard normals [n][A] (null: Philox)
+    int npol;
+};
+
+// row `pol` of the noise table as a Noise (td7f_noise_row is 10 words); only
+// *sigma and *counter change during a launch, and noise_rows loads those
+__device__ __forceinline__ Noise noise_at(const td7f_noise_row *tab, int pol, float scale, const float *z) {
+    static_assert(sizeof(td7f_noise_row) == 40, "td7f_noise_row: u64, 2 x u32, 2 pointers, 2 floats");
+    const uint32_t *p = (const uint32_t *)(tab + pol);
+    uint32_t w[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) w[k] = ldg(p + k);
+    Noise nz;
+    nz.seed = (unsigned long long)uni(w[0]) | ((unsigned long long)uni(w[1]) << 32);
+    nz.tag = uni(w[2]);
+    nz.counter = uni_ptr<unsigned long long>(w + 4);
+    nz.ticket = nullptr;
+    nz.sigma = uni_ptr<float>(w + 6);
+    nz.sigma_dec = __uint_as_float(uni(w[8]));
+    nz.clip = __uint_as_float(uni(w[9]));
+    nz.scale = scale;
+    nz.z = z;
+    nz.dec_count = nullptr;
+    return nz;
+}
+
+// select_multi_kernel's rows with policy pol's own noise (noise_rows, Philox
+// elements counted from seg[pol]); the last workgroup out advances the policies.
+template <int P, int TH>
+__global__ __launch_bounds__(NTH) void select_multi_noise_kernel(SelectMultiNoiseArgs m) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int rows = TR;
+    const SelectMultiArgs &a = m.s;
+    int pol, row0, rend;
+    tile_at(a.tiles, pol, row0, rend);
+    select_multi_rows<P, TH>(lds, a, pol, row0, rend);
+    // noise_rows as it stands, on the segment as a tensor of its own: with the
+    // rows counted from seg0 its element (row * A + c) is the segment-local
+    // one, and out / z moved to the segment's first row put it back
+    const int seg0 = (int)uni((uint32_t)ldg(m.seg + pol));
+    const size_t off = (size_t)seg0 * a.A;
+    const Noise nz = noise_at(m.nzt, pol, a.scale, m.z ? m.z + off : nullptr);
+    noise_rows<P>(lds, a.FT, a.A, rows, row0 - seg0, rend - seg0, nz, a.out + off, NO16, 0, NO16, 0, false);
+    // (noise_rows ended with a barrier: every thread of this workgroup has
+    // read its sigma and counter, and the LDS images are dead)
+    int *last = (int *)lds;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        *last = atomicAdd(m.ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!*last) return;
+    // every workgroup has read its policy's state before its ticket: advance
+    // the policies that acted, thread k policy k (vector lanes, plain stores)
+    for (int k = threadIdx.x; k < m.npol; k += NTH) {
+        if (ldg(m.seg + k + 1) <= ldg(m.seg + k)) continue;
+        const td7f_noise_row *r = m.nzt + k;
+        float *sg = ldg(&r->sigma);
+        unsigned long long *cnt = ldg(&r->counter);
+        *sg = ldg(sg) - ldg(&r->sigma_dec);
+        if (!m.z) *cnt = ldg(cnt) + 1ull;
+    }
+    if (threadIdx.x == 0) *m.ticket = 0u;
 }
 
 }  // namespace td7f
@@ -161,9 +263,26 @@ int td7f_multi_policy_table(int32_t npol, const td7f_lin *enc, const td7f_lin *a
     return EXO_OK;
 }
 
-int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
+// The host image of the noise table from per-policy td7f_noise structs: the
+// one place that fixes noise_at's layout on the host side.
+int td7f_multi_noise_table(int32_t npol, const td7f_noise *noise, td7f_noise_row *table) {
+    if (npol <= 0 || !noise || !table) return EXO_EINVAL;
+    for (int p = 0; p < npol; ++p) {
+        // one ticket, one scale and one z serve the launch; no per-env decay count
+        if (noise[p].z || noise[p].dec_count) return EXO_EINVAL;
+        table[p] = td7f_noise_row{noise[p].seed, noise[p].tag, 0u, noise[p].counter, noise[p].sigma,
+                                  noise[p].sigma_dec, noise[p].clip};
+    }
+    return EXO_OK;
+}
+
+}  // extern "C"
+
+// td7f_select_multi's argument checks and LDS plan (select_impl's at RT = 1)
+// into a; th: tiles per wave.  EXO_OK or the error to return.
+static int multi_plan(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
                       const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
-                      const float *obs, int32_t n, const td7f_noise *noise, float *out, float scale, void *stream) {
+                      const float *obs, int32_t n, float *out, float scale, SelectMultiArgs &a, int &th) {
     const bool prec_ok = prec == PREC_BF16 || prec == PREC_F16 || prec == PREC_F32;
     if (!prec_ok || !act || npol <= 0 || !enc || !actor || !policies_dev || !seg || !tiles_dev || !obs || !out ||
         n <= 0)
@@ -176,7 +295,7 @@ int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f
     }
     if (nt != ntiles) return EXO_EINVAL;
     const int kd = kd_of(prec);
-    int th = 0;
+    th = 0;
     for (int p = 0; p < npol; ++p) {
         const td7f_lin *e = enc + 3 * (size_t)p, *c = actor + 4 * (size_t)p;
         td7f_lin all[7] = {e[0], e[1], e[2], c[0], c[1], c[2], c[3]};
@@ -190,7 +309,7 @@ int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f
             if (x.n_out != y.n_out || x.n_in != y.n_in || x.ksf != y.ksf) return EXO_EINVAL;
         }
     }
-    SelectMultiArgs a{};
+    a = SelectMultiArgs{};
     a.pol = (const td7f_lin *)policies_dev;
     a.tiles = tiles_dev;
     a.act_enc = act[0];
@@ -203,8 +322,6 @@ int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f
     if (actor[0].n_in != a.S || actor[1].n_in != a.Ha + a.Z || a.A > THIN_NC || a.S > NTH) return EXO_EINVAL;
     if ((long)n * a.A >= (1L << 31)) return EXO_ERANGE;  // the Philox element index is 32 bits
     a.out = out;
-    a.noisy = noise != nullptr;
-    if (noise) a.nz = noise_of(*noise);
     a.scale = scale;
     // select_impl's plan at RT = 1
     const int rows = TR, hmax = std::max(enc[0].n_out, std::max(enc[1].n_out, std::max(a.Ha, actor[1].n_out)));
@@ -222,7 +339,46 @@ int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f
     a.TW = b.r32(THIN_NC, actor[3].n_in);
     a.FT = b.r32(rows, 16);
     a.lds_bytes = b.off;
-    return DISPATCH(prec, th, select_multi_kernel, dim3((unsigned)ntiles), b.off, a, (hipStream_t)stream);
+    return EXO_OK;
+}
+
+extern "C" {
+
+int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
+                      const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
+                      const float *obs, int32_t n, const td7f_noise *noise, float *out, float scale, void *stream) {
+    SelectMultiArgs a;
+    int th;
+    const int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
+                              a, th);
+    if (rc != EXO_OK) return rc;
+    a.noisy = noise != nullptr;
+    if (noise) a.nz = noise_of(*noise);
+    return DISPATCH(prec, th, select_multi_kernel, dim3((unsigned)ntiles), a.lds_bytes, a, (hipStream_t)stream);
+}
+
+int td7f_select_multi_noise(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc,
+                            const td7f_lin *actor, const void *policies_dev, const int32_t *seg,
+                            const int32_t *tiles_dev, int32_t ntiles, const float *obs, int32_t n,
+                            const td7f_noise_row *noise, const void *noise_dev, const int32_t *seg_dev,
+                            uint32_t *ticket_dev, const float *z_dev, float *out, float scale, void *stream) {
+    SelectMultiNoiseArgs m{};
+    int th;
+    const int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
+                              m.s, th);
+    if (rc != EXO_OK) return rc;
+    if (!noise || !noise_dev || !seg_dev || !ticket_dev) return EXO_EINVAL;
+    for (int p = 0; p < npol; ++p) {
+        if (!(noise[p].sigma_dec >= 0.f) || !(noise[p].clip >= 0.f)) return EXO_EINVAL;
+        if (seg[p + 1] > seg[p] && (!noise[p].sigma || !noise[p].counter)) return EXO_EINVAL;
+    }
+    m.nzt = (const td7f_noise_row *)noise_dev;
+    m.seg = seg_dev;
+    m.ticket = ticket_dev;
+    m.z = z_dev;
+    m.npol = npol;
+    return DISPATCH(prec, th, select_multi_noise_kernel, dim3((unsigned)ntiles), m.s.lds_bytes, m,
+                    (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -25,4 +25,8 @@ def __getattr__(name):
     if name == "Evaluator":
         from .evaluate import Evaluator
         return Evaluator
+    # dataset collection from many noisy behaviour policies (exo_amd.collect)
+    if name == "Collector":
+        from .collect import Collector
+        return Collector
     raise AttributeError(f"module 'exo_amd' has no attribute {name!r}")

@@ -72,6 +72,12 @@ class TD7FNoise(ctypes.Structure):
                 ("dec_count", c_void_p)]
 
 
+class TD7FNoiseRow(ctypes.Structure):
+    """td7f_noise_row (include/exo_amd.h)."""
+    _fields_ = [("seed", c_uint64), ("tag", ctypes.c_uint32), ("pad0", ctypes.c_uint32), ("counter", c_void_p),
+                ("sigma", c_void_p), ("sigma_dec", ctypes.c_float), ("clip", ctypes.c_float)]
+
+
 class TD7FXT(ctypes.Structure):
     """td7f_xt (include/exo_amd.h)."""
     _fields_ = [("x", c_void_p), ("dp", c_void_p), ("part", c_void_p)]
@@ -242,6 +248,10 @@ EXPORTS = {
                                     c_void_p]),
     "td7f_multi_tiles": (c_int32, [c_int32, P(c_int32), P(c_int32), c_int32]),
     "td7f_multi_policy_table": (c_int32, [c_int32, P(TD7FLin), P(TD7FLin), P(TD7FLin)]),
+    "td7f_select_multi_noise": (c_int32, [c_int32, P(c_int32), c_int32, P(TD7FLin), P(TD7FLin), c_void_p, P(c_int32),
+                                          c_void_p, c_int32, c_void_p, c_int32, P(TD7FNoiseRow), c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
+    "td7f_multi_noise_table": (c_int32, [c_int32, P(TD7FNoise), P(TD7FNoiseRow)]),
     "td7f_target": (c_int32, [c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), P(TD7FLin), c_void_p, c_int32,
                               P(TD7FNoise), c_void_p, c_void_p, c_void_p]),
     "td7f_fixed": (c_int32, [c_int32, P(c_int32), P(TD7FLin), c_void_p, c_void_p, c_int32, c_void_p, c_void_p,

@@ -15,6 +15,33 @@ from . import graphs
 from .vec_env import VecExoskeletonEnv
 
 
+def segment_layout(K, envs_per_policy, env_kwargs=None, per_policy_env_kwargs=None, owner="Evaluator"):
+    """One env batch for K policies (Evaluator, Collector): policy p's envs are
+    the contiguous rows [seg[p], seg[p+1]), env i of a segment follows motion
+    i % 8, env_kwargs go to every env and per_policy_env_kwargs[p] (a dict) to
+    policy p's envs, concatenated per segment.  envs_per_policy: one count or
+    K.  Returns (seg: K + 1 ints, motions: int64 [n], the env keyword
+    arguments).  Host only."""
+    if isinstance(envs_per_policy, (int, np.integer)):
+        envs_per_policy = [int(envs_per_policy)] * K
+    counts = [int(c) for c in envs_per_policy]
+    if len(counts) != K or min(counts) < 0 or sum(counts) <= 0:
+        raise ValueError(f"{owner}: envs_per_policy must hold {K} non-negative counts, not all zero")
+    seg = [0] + [int(v) for v in np.cumsum(counts)]
+    kw = dict(env_kwargs or {})
+    if per_policy_env_kwargs is not None:
+        if len(per_policy_env_kwargs) != K:
+            raise ValueError(f"{owner}: per_policy_env_kwargs must hold {K} dicts")
+        names = set().union(*[set(d) for d in per_policy_env_kwargs])
+        for name in names:
+            if any(name not in d for d in per_policy_env_kwargs):
+                raise ValueError(f"{owner}: per_policy_env_kwargs: {name!r} is not given for every policy")
+            vals = [np.asarray(d[name], dtype=np.float64) for d in per_policy_env_kwargs]
+            kw[name] = np.concatenate([np.broadcast_to(v, (c,) + v.shape) for v, c in zip(vals, counts)], axis=0)
+    motions = np.concatenate([np.arange(c) % 8 for c in counts]).astype(np.int64)
+    return seg, motions, kw
+
+
 class Evaluator:
     """Evaluator(policy_set, envs_per_policy, ...): policy p's envs are the
     contiguous rows [seg[p], seg[p+1]) of one VecExoskeletonEnv; env i of a
@@ -31,28 +58,12 @@ class Evaluator:
     def __init__(self, policy_set, envs_per_policy, env_kwargs=None, per_policy_env_kwargs=None, seed=0,
                  physics="ideal", max_action=1.0, graph=False):
         K = len(policy_set)
-        if isinstance(envs_per_policy, (int, np.integer)):
-            envs_per_policy = [int(envs_per_policy)] * K
-        counts = [int(c) for c in envs_per_policy]
-        if len(counts) != K or min(counts) < 0 or sum(counts) <= 0:
-            raise ValueError(f"Evaluator: envs_per_policy must hold {K} non-negative counts, not all zero")
+        self.seg, motions, kw = segment_layout(K, envs_per_policy, env_kwargs, per_policy_env_kwargs, "Evaluator")
         self.policy_set = policy_set
-        self.seg = [0] + [int(v) for v in np.cumsum(counts)]
         self.n = self.seg[-1]
         self.seed = int(seed)
         self.max_action = float(max_action)
         self.device = policy_set.dev
-        kw = dict(env_kwargs or {})
-        if per_policy_env_kwargs is not None:
-            if len(per_policy_env_kwargs) != K:
-                raise ValueError(f"Evaluator: per_policy_env_kwargs must hold {K} dicts")
-            names = set().union(*[set(d) for d in per_policy_env_kwargs])
-            for name in names:
-                if any(name not in d for d in per_policy_env_kwargs):
-                    raise ValueError(f"Evaluator: per_policy_env_kwargs: {name!r} is not given for every policy")
-                vals = [np.asarray(d[name], dtype=np.float64) for d in per_policy_env_kwargs]
-                kw[name] = np.concatenate([np.broadcast_to(v, (c,) + v.shape) for v, c in zip(vals, counts)], axis=0)
-        motions = np.concatenate([np.arange(c) % 8 for c in counts]).astype(np.int64)
         self.env = VecExoskeletonEnv(self.n, motions=motions, seed=self.seed, device=self.device, physics=physics,
                                      **kw)
         d = self.device

@@ -672,6 +672,104 @@ def select_multi_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles
                                        float(scale), nat.stream_ptr(obs.device))
 
 
+def per_policy(value, K, name, owner="MultiNoise"):
+    """A scalar or a length-K sequence as a list of K floats, none negative
+    (sigma, sigma_dec, clip of K behaviour policies)."""
+    v = np.asarray(value, dtype=np.float64)
+    if v.ndim == 0:
+        v = np.full((K,), float(v))
+    if v.shape != (K,):
+        raise ValueError(f"{owner}: {name} must be a scalar or hold {K} values")
+    if not np.all(np.isfinite(v)) or np.any(v < 0):
+        raise ValueError(f"{owner}: {name} must be finite and >= 0")
+    return [float(x) for x in v]
+
+
+# The tags of the Philox streams a MultiNoise owns: policy p draws from tag
+# MULTI_NOISE_TAG0 + p.  The project's other consumers use small tags (the
+# learner's exploration stream is 2, the replay's sampler and the target noise
+# sit next to it), so no policy shares a stream with them or with another
+# policy of the set.
+MULTI_NOISE_TAG0 = 0x4D4E0000
+
+
+class MultiNoise:
+    """One exploration-noise state per policy of a PolicySet, for
+    PolicySet.act(noise=...) (td7f_select_multi_noise): policy p's rows get
+    clamp(a + c_p(z * sigma_p), -1, 1) * scale with z from policy p's own
+    Philox stream, element (row - seg[p]) * A + column -- TD7_multi_agent.py
+    :192-209 per policy.  After a launch every policy that had rows has
+    sigma_p -= sigma_dec_p and its call counter advanced.
+
+    sigma, sigma_dec, clip: scalars or length-K sequences.  By default the
+    object owns one ops.DeviceRNG per policy (tags: tags, default
+    MULTI_NOISE_TAG0 + p, all distinct) and one fp32 [K] sigma tensor.
+    states=[(rng, sigma_tensor), ...] binds existing state instead -- e.g. an
+    agent's learner._explore_rng / exploration_noise_t -- and `sigma` is then
+    ignored (None).  The device table is built once; it holds pointers, so the
+    bound tensors must stay alive and in place."""
+
+    def __init__(self, policy_set, sigma, sigma_dec=0.0, clip=0.0, tags=None, states=None):
+        K = len(policy_set)
+        self.K = K
+        self.dev = policy_set.dev
+        self.sigma_dec = per_policy(sigma_dec, K, "sigma_dec")
+        self.clip = per_policy(clip, K, "clip")
+        if states is not None:
+            states = list(states)
+            if len(states) != K:
+                raise ValueError(f"MultiNoise: states must hold {K} (rng, sigma) pairs")
+            self.rngs = [s[0] for s in states]
+            self.sigmas = [s[1] for s in states]
+            for t in self.sigmas:
+                if t.dtype != torch.float32 or t.numel() != 1 or t.device != self.dev:
+                    raise ValueError(f"MultiNoise: a bound sigma must be one float32 on {self.dev}")
+            self.sigma = None
+            self.owns_state = False
+        else:
+            if tags is None:
+                tags = [MULTI_NOISE_TAG0 + p for p in range(K)]
+            tags = [int(t) for t in tags]
+            if len(tags) != K or len(set(t & 0xFFFFFFFF for t in tags)) != K:
+                raise ValueError(f"MultiNoise: tags must hold {K} distinct values")
+            self.sigma0 = per_policy(sigma, K, "sigma")
+            self.rngs = [ops.DeviceRNG(self.dev, t) for t in tags]
+            self.sigma = torch.tensor(self.sigma0, dtype=torch.float32, device=self.dev)
+            self.sigmas = [self.sigma[p:p + 1] for p in range(K)]
+            self.owns_state = True
+        # one ticket word for the launch (zero between launches)
+        self.ticket = torch.zeros((2,), dtype=torch.int32, device=self.dev)
+        per = (TD7FNoise * K)(*[TD7FNoise(r.seed, r.tag, 0, r.counter_ptr, None, s.data_ptr(), d, c, 1.0, 0, None,
+                                          None)
+                                for r, s, d, c in zip(self.rngs, self.sigmas, self.sigma_dec, self.clip)])
+        self.rows = (nat.TD7FNoiseRow * K)()
+        nat.check(nat.lib().td7f_multi_noise_table(K, per, self.rows), "td7f_multi_noise_table")
+        self.table = torch.frombuffer(bytearray(bytes(self.rows)), dtype=torch.uint8).to(self.dev)
+
+    def sigma_now(self):
+        """every policy's sigma (one host read per bound tensor, or one)"""
+        if self.sigma is not None:
+            return [float(v) for v in self.sigma.cpu()]
+        return [float(t) for t in self.sigmas]
+
+    def counters(self):
+        """every policy's call counter (host reads)"""
+        return [int(r.state[0]) for r in self.rngs]
+
+
+def select_multi_noise_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, rows, noise_dev,
+                           seg_dev, ticket, z, out, scale, npol=None):
+    """td7f_select_multi_noise as it stands in the C ABI; returns its status
+    code.  rows: the host TD7FNoiseRow array (or None), noise_dev / seg_dev /
+    ticket / z: device tensors (or None)."""
+    npol = len(seg) - 1 if npol is None else npol
+    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
+    return nat.lib().td7f_select_multi_noise(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg,
+                                             nat.ptr(tiles_dev), int(ntiles), nat.ptr(obs), int(n), rows,
+                                             nat.ptr(noise_dev), nat.ptr(seg_dev), nat.ptr(ticket), nat.ptr(z),
+                                             nat.ptr(out), float(scale), nat.stream_ptr(obs.device))
+
+
 class PolicySet:
     """K policies -- (actor, fixed encoder) module pairs of one shape -- packed
     for td7f_select_multi: one launch in which policy p acts on the rows
@@ -745,6 +843,7 @@ class PolicySet:
         try:
             try:
                 self.act(obs, seg)
+                self.act(obs, seg, noise=MultiNoise(self, 0.0))
             except RuntimeError as e:
                 raise PlanError(f"td7f_select_multi cannot run this policy shape: {e}") from e
         finally:
@@ -783,16 +882,25 @@ class PolicySet:
             t = multi_tiles(np.asarray(key, dtype=np.int64))
             # (an empty table still needs an address)
             dev = torch.as_tensor(t if len(t) else np.zeros((1, 3), np.int32)).to(self.dev)
-            hit = self._tiles[key] = (dev, len(t))
+            # the device copy of seg td7f_select_multi_noise reads, built with the tile table
+            hit = self._tiles[key] = (dev, len(t), torch.tensor(key, dtype=torch.int32).to(self.dev))
         return key, hit[0], hit[1]
 
+    def seg_dev(self, seg):
+        """the device copy of seg (int32 [K + 1]) cached with its tile table"""
+        key, _, _ = self.tiles(seg)
+        return self._tiles[key][2]
+
     @torch.no_grad()
-    def act(self, obs, seg, out=None, scale=1.0, noise=None):
+    def act(self, obs, seg, out=None, scale=1.0, noise=None, z=None):
         """One td7f_select_multi launch: out[r] = policy p's action for obs[r],
         seg[p] <= r < seg[p+1].  noise None: deterministic, clamp(tanh(.), -1,
         1) * scale, no noise state touched; a TD7FNoise (FusedNets._noise):
         that one exploration-noise state for the whole launch (its own scale
-        applies).  Repack changed weights with refresh() first."""
+        applies); a MultiNoise: every policy its own state
+        (td7f_select_multi_noise), times `scale`, and z (float32 [n, A]
+        standard normals) then replaces the Philox draws and leaves the
+        counters alone.  Repack changed weights with refresh() first."""
         key, tiles, nt = self.tiles(seg)
         obs = obs.contiguous()
         n = obs.shape[0]
@@ -802,6 +910,18 @@ class PolicySet:
             out = torch.empty((n, self.A), dtype=torch.float32, device=obs.device)
         elif tuple(out.shape) != (n, self.A) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError(f"PolicySet.act: out must be contiguous float32 {(n, self.A)}")
+        if isinstance(noise, MultiNoise):
+            if noise.K != len(self):
+                raise ValueError(f"PolicySet.act: the MultiNoise holds {noise.K} policies, the set {len(self)}")
+            if z is not None and (tuple(z.shape) != (n, self.A) or z.dtype != torch.float32
+                                  or not z.is_contiguous() or z.device != obs.device):
+                raise ValueError(f"PolicySet.act: z must be contiguous float32 {(n, self.A)} on {obs.device}")
+            nat.check(select_multi_noise_raw(self.prec, self.act_codes, self.enc, self.actor, self.table, key, tiles,
+                                             nt, obs, n, noise.rows, noise.table, self._tiles[key][2], noise.ticket,
+                                             z, out, scale), "td7f_select_multi_noise")
+            return out
+        if z is not None:
+            raise ValueError("PolicySet.act: z goes with a MultiNoise")
         nat.check(select_multi_raw(self.prec, self.act_codes, self.enc, self.actor, self.table, key, tiles, nt, obs,
                                    n, noise, out, scale), "td7f_select_multi")
         return out

@@ -763,8 +763,9 @@ int td7f_select_part(int32_t prec, const int32_t *act, const td7f_lin *enc, cons
  * noise with that one noise state for the whole launch (Philox element =
  * global row * A + column, so npol = 1 equals td7f_select at rt = 1 bit for
  * bit; sigma and the call counter advance once, by the last workgroup out);
- * `scale` is then unused (noise->scale applies).  A sigma per policy is out of
- * scope: one td7f_noise serves the launch. */
+ * `scale` is then unused (noise->scale applies).  One td7f_noise serves this
+ * launch; td7f_select_multi_noise below gives every policy its own sigma,
+ * clip, decay and random stream. */
 int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
                       const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
                       const float *obs_dev, int32_t n, const td7f_noise *noise, float *act_out_dev, float scale,
@@ -781,6 +782,56 @@ int td7f_multi_tiles(int32_t npol, const int32_t *seg, int32_t *tiles, int32_t c
  * td7f_select_multi, so that what the host validates is what the kernel
  * reads. */
 int td7f_multi_policy_table(int32_t npol, const td7f_lin *enc, const td7f_lin *actor, td7f_lin *table);
+/* One row of td7f_select_multi_noise's noise table: the exploration-noise
+ * state of one policy (TD7_multi_agent.py:192-209: the Gaussian of :203-206
+ * with that agent's exploration_noise and its decay).  counter and sigma go by
+ * pointer, as in td7f_noise: a row may point at state the caller shares with
+ * td7f_select. */
+typedef struct {
+    uint64_t seed;
+    uint32_t tag, pad0;
+    unsigned long long *counter;
+    float *sigma;
+    float sigma_dec, clip;
+} td7f_noise_row;
+/* td7f_select_multi with one exploration-noise state per policy
+ * (TD7_multi_agent.py:192-209 per policy, noise included): row r of policy p,
+ * column c, gets act_out = clamp(a + c_p(z * *sigma_p), -1, 1) * scale with
+ * c_p = clamp(+-clip_p) when clip_p > 0 and z normal i % 2 of Philox block
+ * i / 2, i = (r - seg[p]) * A + c, of call *counter_p of the stream (seed_p,
+ * tag_p): td7f_noise's arithmetic with a segment-local element, so policy p's
+ * rows equal td7f_select (rt = 1) of those rows alone with the same noise
+ * state, bit for bit, whichever policies share the launch and wherever its
+ * segment starts.  The last workgroup out (ticket_dev, one zeroed word that
+ * the launch leaves zero) advances every policy whose segment is not empty:
+ * *sigma_p -= sigma_dec_p, *counter_p += 1; an empty segment's state is
+ * neither read nor written.  z_dev non-NULL: the standard normals are given
+ * (fp32 [n][A], z_dev[r * A + c], the global element) and no counter moves.
+ *
+ * Besides td7f_select_multi's arguments and tables:
+ *   noise      host [npol] rows, what the call validates;
+ *   noise_dev  their byte copy in device memory (td7f_multi_noise_table
+ *              writes the host image), what the kernel reads;
+ *   seg_dev    int32 [npol + 1], a device copy of seg.
+ * EXO_EINVAL, nothing launched: td7f_select_multi's cases; a NULL noise,
+ * noise_dev, seg_dev or ticket_dev; sigma_dec < 0 or clip < 0 in any row; a
+ * NULL sigma or counter in a row whose segment is not empty.  Like
+ * td7f_select_multi the call allocates nothing and copies nothing to the
+ * device, and td7f_probe makes it validate and return. */
+int td7f_select_multi_noise(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc,
+                            const td7f_lin *actor, const void *policies_dev, const int32_t *seg,
+                            const int32_t *tiles_dev, int32_t ntiles, const float *obs_dev, int32_t n,
+                            const td7f_noise_row *noise, const void *noise_dev, const int32_t *seg_dev,
+                            uint32_t *ticket_dev, const float *z_dev, float *act_out_dev, float scale,
+                            void *stream);
+/* The host image of td7f_select_multi_noise's noise table, table [npol]
+ * (host), from one td7f_noise per policy (TD7_multi_agent.py:192-209: each
+ * agent's own exploration state): seed, tag, counter, sigma, sigma_dec and
+ * clip are taken; ticket and scale are the launch's and ignored; a non-NULL z
+ * or dec_count is EXO_EINVAL.  Pass the same table to the launch as `noise`
+ * and its device copy as `noise_dev`, so that what the host validates is what
+ * the kernel reads. */
+int td7f_multi_noise_table(int32_t npol, const td7f_noise *noise, td7f_noise_row *table);
 /* The critic target chain (TD7_multi_agent.py:233-241): fixed_target_zs(s'),
  * next_action = actor_target(s', zs) + clipped noise, fixed_target_zsa and both
  * heads of critic_target -> qt_dev [B][2].  tenc: zs1..zs3, zsa1..zsa3;
