@@ -41,6 +41,13 @@
 //                starts -- its rows equal its own td7f_select, noise included.
 //   ticket       one word for the launch: the last workgroup out advances
 //                every policy with a non-empty segment (thread k policy k).
+//
+//   td7f_select_multi_seq : the same launch with a coloured noise sequence per
+//                       env (TD7_multi_agent_Pink_noise.py:203-228): the noise
+//                       term of row r is column t[r] of its row of the table
+//                       td7f_pink_advance (td7_pink.hip) keeps, already scaled
+//                       by sigma; the ticket advances sigma only, no Philox
+//                       counter moves.
 #include "td7_fused.h"
 
 #include <algorithm>
@@ -230,6 +237,65 @@ __global__ __launch_bounds__(NTH) void select_multi_noise_kernel(SelectMultiNois
     if (threadIdx.x == 0) *m.ticket = 0u;
 }
 
+// ---- a coloured sequence per env (td7f_select_multi_seq)
+struct SelectMultiSeqArgs {
+    SelectMultiArgs s;          // s.nz / s.noisy unused
+    const td7f_noise_row *nzt;  // device [npol]: sigma, sigma_dec, clip (no Philox state is touched)
+    const int *seg;             // device [npol + 1]
+    uint32_t *ticket;
+    const float *seq;  // [n][Lmax][A], td7f_pink_advance's table
+    const int *t;      // [n] step index of each env's episode
+    int Lmax, npol;
+};
+
+// noise_rows' sibling for a noise term that is already scaled: global row R =
+// row0 + row of the fp32 actions a gets e = seq[R][min(t[R], Lmax - 1)][c],
+// clamped to +-clip when clip > 0; out = clamp(a + e, -1, 1) * scale.  Ends
+// with a barrier, no ticket.
+__device__ __forceinline__ void seq_rows(char *lds, R32 a, int A, int rows, int row0, int rend, const float *seq,
+                                         const int *t, int Lmax, float clip, float scale, float *out) {
+    for (int k = threadIdx.x; k < rows * A; k += NTH) {
+        const int row = k / A, c = k - row * A, R = row0 + row;
+        if (R < rend) {
+            const int tt = min(max(ldg(t + R), 0), Lmax - 1);
+            float e = ldg(seq + ((size_t)R * Lmax + tt) * A + c);
+            if (clip > 0.f) e = fminf(fmaxf(e, -clip), clip);
+            stg(out + (size_t)R * A + c, fminf(fmaxf(*p32(lds, a, row, c) + e, -1.0f), 1.0f) * scale);
+        }
+    }
+    __syncthreads();
+}
+
+// select_multi_kernel's rows plus each env's own column of its coloured
+// sequence; the last workgroup out advances sigma of the policies with rows.
+template <int P, int TH>
+__global__ __launch_bounds__(NTH) void select_multi_seq_kernel(SelectMultiSeqArgs m) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int rows = TR;
+    const SelectMultiArgs &a = m.s;
+    int pol, row0, rend;
+    tile_at(a.tiles, pol, row0, rend);
+    select_multi_rows<P, TH>(lds, a, pol, row0, rend);
+    const float clip = __uint_as_float(uni(ldg((const uint32_t *)(m.nzt + pol) + 9)));
+    seq_rows(lds, a.FT, a.A, rows, row0, rend, m.seq, m.t, m.Lmax, clip, a.scale, a.out);
+    // (seq_rows ended with a barrier: the LDS images are dead)
+    int *last = (int *)lds;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        *last = atomicAdd(m.ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!*last) return;
+    // sigma is read by td7f_pink_advance only, between launches: thread k policy k
+    for (int k = threadIdx.x; k < m.npol; k += NTH) {
+        if (ldg(m.seg + k + 1) <= ldg(m.seg + k)) continue;
+        const td7f_noise_row *r = m.nzt + k;
+        float *sg = ldg(&r->sigma);
+        *sg = ldg(sg) - ldg(&r->sigma_dec);
+    }
+    if (threadIdx.x == 0) *m.ticket = 0u;
+}
+
 }  // namespace td7f
 
 using namespace td7f;
@@ -378,6 +444,32 @@ int td7f_select_multi_noise(int32_t prec, const int32_t *act, int32_t npol, cons
     m.z = z_dev;
     m.npol = npol;
     return DISPATCH(prec, th, select_multi_noise_kernel, dim3((unsigned)ntiles), m.s.lds_bytes, m,
+                    (hipStream_t)stream);
+}
+
+int td7f_select_multi_seq(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
+                          const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
+                          const float *obs, int32_t n, const td7f_noise_row *noise, const void *noise_dev,
+                          const int32_t *seg_dev, uint32_t *ticket_dev, const float *seq_dev, const int32_t *t_dev,
+                          int32_t Lmax, float *out, float scale, void *stream) {
+    SelectMultiSeqArgs m{};
+    int th;
+    const int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
+                              m.s, th);
+    if (rc != EXO_OK) return rc;
+    if (!noise || !noise_dev || !seg_dev || !ticket_dev || !seq_dev || !t_dev || Lmax <= 0) return EXO_EINVAL;
+    for (int p = 0; p < npol; ++p) {
+        if (!(noise[p].sigma_dec >= 0.f) || !(noise[p].clip >= 0.f)) return EXO_EINVAL;
+        if (seg[p + 1] > seg[p] && !noise[p].sigma) return EXO_EINVAL;
+    }
+    m.nzt = (const td7f_noise_row *)noise_dev;
+    m.seg = seg_dev;
+    m.ticket = ticket_dev;
+    m.seq = seq_dev;
+    m.t = t_dev;
+    m.Lmax = Lmax;
+    m.npol = npol;
+    return DISPATCH(prec, th, select_multi_seq_kernel, dim3((unsigned)ntiles), m.s.lds_bytes, m,
                     (hipStream_t)stream);
 }
 

@@ -29,4 +29,8 @@ def __getattr__(name):
     if name == "Collector":
         from .collect import Collector
         return Collector
+    # a coloured exploration-noise sequence per env (exo_amd.fused)
+    if name == "PinkNoise":
+        from .fused import PinkNoise
+        return PinkNoise
     raise AttributeError(f"module 'exo_amd' has no attribute {name!r}")

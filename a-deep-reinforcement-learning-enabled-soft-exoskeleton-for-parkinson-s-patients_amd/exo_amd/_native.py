@@ -252,6 +252,11 @@ EXPORTS = {
                                           c_void_p, c_int32, c_void_p, c_int32, P(TD7FNoiseRow), c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p]),
     "td7f_multi_noise_table": (c_int32, [c_int32, P(TD7FNoise), P(TD7FNoiseRow)]),
+    "td7f_pink_advance": (c_int32, [c_int32, P(c_int32), c_int32, c_int32, c_int32, c_int32, P(c_int32)]
+                          + [c_void_p] * 9 + [P(TD7FNoiseRow)] + [c_void_p] * 6),
+    "td7f_select_multi_seq": (c_int32, [c_int32, P(c_int32), c_int32, P(TD7FLin), P(TD7FLin), c_void_p, P(c_int32),
+                                        c_void_p, c_int32, c_void_p, c_int32, P(TD7FNoiseRow), c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_int32, c_void_p, ctypes.c_float, c_void_p]),
     "td7f_target": (c_int32, [c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), P(TD7FLin), c_void_p, c_int32,
                               P(TD7FNoise), c_void_p, c_void_p, c_void_p]),
     "td7f_fixed": (c_int32, [c_int32, P(c_int32), P(TD7FLin), c_void_p, c_void_p, c_int32, c_void_p, c_void_p,

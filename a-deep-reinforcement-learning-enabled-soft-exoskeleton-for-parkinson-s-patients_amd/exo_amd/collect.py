@@ -17,6 +17,7 @@ from . import graphs
 from .evaluate import segment_layout
 
 PHYSICS = ("ideal", "multibody")
+NOISES = ("gaussian", "pink")
 
 
 def check_sigma_schedule(sigma, sigma_dec, steps, counts=None):
@@ -47,6 +48,12 @@ class Collector:
     every env, per_policy_env_kwargs[p] to policy p's (evaluate.segment_layout).
     sigma, sigma_dec, clip: scalars or one value per policy (fused.MultiNoise,
     which the collector owns: policy p draws from tag MULTI_NOISE_TAG0 + p).
+    noise="pink": instead of white noise, one coloured sequence (power-law
+    exponent beta) per env and episode, of the env's motion length, scaled by
+    its policy's sigma at the episode's start (fused.PinkNoise;
+    TD7_multi_agent_Pink_noise.py:203-228); after the statistics of a step one
+    td7f_pink_advance launch counts the steps and regenerates the sequences of
+    the envs that finished, on the device.
 
     replay: a replay.LAP of the policies' state / action dimensions, e.g.
     agent.replay_buffer; env i's rows go to stratum strata[i] (int32 [n],
@@ -57,12 +64,15 @@ class Collector:
     no side streams); release() destroys them through graphs.release_graphs."""
 
     def __init__(self, policy_set, envs_per_policy, replay, sigma=0.1, sigma_dec=0.0, clip=0.0, env_kwargs=None,
-                 per_policy_env_kwargs=None, seed=0, physics="ideal", max_action=1.0, strata=None, graph=False):
-        from .fused import MultiNoise, per_policy
+                 per_policy_env_kwargs=None, seed=0, physics="ideal", max_action=1.0, strata=None, graph=False,
+                 noise="gaussian", beta=1.0):
+        from .fused import MultiNoise, PinkNoise, per_policy
         from .vec_env import VecExoskeletonEnv
         K = len(policy_set)
         if physics not in PHYSICS:
             raise ValueError(f"Collector: physics must be one of {PHYSICS}, not {physics!r}")
+        if noise not in NOISES:
+            raise ValueError(f"Collector: noise must be one of {NOISES}, not {noise!r}")
         sig = per_policy(sigma, K, "sigma", "Collector")
         dec = per_policy(sigma_dec, K, "sigma_dec", "Collector")
         per_policy(clip, K, "clip", "Collector")
@@ -87,7 +97,12 @@ class Collector:
         self.device = d = policy_set.dev
         self._sigma_host, self._dec_host = sig, dec  # the schedule as set here (check_sigma_schedule)
         self.env = VecExoskeletonEnv(self.n, motions=motions, seed=self.seed, device=d, physics=physics, **kw)
-        self.noise = MultiNoise(policy_set, sig, dec, clip)
+        self.noise_kind = noise
+        if noise == "pink":
+            # one sequence per env, of its motion's length, regenerated on the device when its episode ends
+            self.noise = PinkNoise(policy_set, self.seg, self.env.lengths_host, sig, dec, clip, beta=beta)
+        else:
+            self.noise = MultiNoise(policy_set, sig, dec, clip)
         self.strata = torch.as_tensor(strata_h, device=d)
         # two observation buffers used in alternation (VecTrainer): step c reads
         # obs[c], the env writes the next observation into obs[1 - c]
@@ -160,6 +175,8 @@ class Collector:
         self._first_open.logical_xor_(self._tb)
         self._ret32.masked_fill_(done, 0.0)
         self._ret64.masked_fill_(done, 0.0)
+        if self.noise_kind == "pink":
+            self.noise.advance(self.active, done)
         self.env.episode_advance(self.active, self.active_count, out[0], self._steps_total)
 
     def _capture(self, c):

@@ -770,6 +770,109 @@ def select_multi_noise_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, 
                                              nat.ptr(out), float(scale), nat.stream_ptr(obs.device))
 
 
+class PinkNoise:
+    """One coloured (power-law, exponent beta) noise sequence per env of a
+    PolicySet layout, for PolicySet.act(noise=...) (td7f_select_multi_seq) --
+    TD7_multi_agent_Pink_noise.py:203-228 per env, with asynchronous episodes:
+    env r of policy p owns the row seq[r] ([Lmax, A]; its first lengths[r]
+    steps are used), peak-normalised and scaled by sigma_p as it stood when the
+    env's episode began; step t[r] of its episode adds seq[r, t[r]].
+    advance(stepped, done) after every env step counts the steps and
+    regenerates the rows of finished episodes (td7f_pink_advance), all on the
+    device: no host read, so a step with it can be captured in a graph.
+
+    seg: the layout PolicySet.act is called with; lengths: every env's
+    sequence length (VecExoskeletonEnv.lengths_host).  sigma, sigma_dec, clip,
+    tags as MultiNoise, whose device table, sigma tensor and DeviceRNGs this
+    object holds (default tags MULTI_NOISE_TAG0 + 0x8000 + p: distinct from a
+    MultiNoise of the same set).  Row r draws from its policy's stream at call
+    epi[r], the index of its episode; the streams' call counters stay 0."""
+
+    def __init__(self, policy_set, seg, lengths, sigma, sigma_dec=0.0, clip=0.0, beta=1.0, tags=None):
+        from . import pink
+        K = len(policy_set)
+        if tags is None:
+            tags = [MULTI_NOISE_TAG0 + 0x8000 + p for p in range(K)]
+        self.multi = MultiNoise(policy_set, sigma, sigma_dec, clip, tags=tags)
+        self.K, self.dev, self.A = K, policy_set.dev, policy_set.A
+        self.table, self.rows, self.ticket = self.multi.table, self.multi.rows, self.multi.ticket
+        self.sigma, self.rngs = self.multi.sigma, self.multi.rngs
+        self.beta = float(beta)
+        self.seg, _, _ = policy_set.tiles(seg)
+        self.seg_dev = policy_set.seg_dev(seg)
+        self.n = n = self.seg[-1]
+        lengths = np.asarray(lengths)
+        if lengths.shape != (n,):
+            raise ValueError(f"PinkNoise: lengths must hold one value for each of the {n} envs")
+        len_cls, cls_len, cls_scale, cls_norm = pink.length_classes(lengths, self.beta)
+        self.lengths_host = lengths.astype(np.int64)
+        self.Lmax = int(cls_len[-1])
+        self.nf_max = self.Lmax // 2 + 1
+        self.cls_len_host = (ctypes.c_int32 * len(cls_len))(*[int(v) for v in cls_len])
+        self._cseg = (ctypes.c_int32 * len(self.seg))(*self.seg)
+        d = self.dev
+        self.len_cls = torch.as_tensor(len_cls).to(d)
+        self.cls_len = torch.as_tensor(cls_len).to(d)
+        self.cls_scale = torch.as_tensor(cls_scale).contiguous().to(d)
+        self.cls_norm = torch.as_tensor(cls_norm).to(d)
+        self.seq = torch.zeros((n, self.Lmax, self.A), dtype=torch.float32, device=d)
+        self.t = torch.zeros((n,), dtype=torch.int32, device=d)
+        # the index of the episode whose sequence a row holds: the fill below is episode 0
+        self.epi = torch.full((n,), -1, dtype=torch.int32, device=d)
+        ones = torch.ones((n,), dtype=torch.bool, device=d)
+        self.advance(ones, ones)
+
+    def sigma_now(self):
+        return self.multi.sigma_now()
+
+    def _mask(self, m, name):
+        if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (self.n,) or m.device != self.dev \
+                or not m.is_contiguous():
+            raise ValueError(f"PinkNoise.advance: {name} must be contiguous bool / uint8 [{self.n}] on {self.dev}")
+        return m
+
+    def _spec(self, s, name):
+        shape = (self.n, self.A, self.nf_max, 2)
+        if s is not None and (tuple(s.shape) != shape or s.dtype != torch.float32 or s.device != self.dev
+                              or not s.is_contiguous()):
+            raise ValueError(f"PinkNoise.advance: {name} must be contiguous float32 {shape} on {self.dev}")
+        return s
+
+    @torch.no_grad()
+    def advance(self, stepped, done, spectrum=None, spec_out=None, peak_out=None):
+        """One td7f_pink_advance launch: t += 1 where stepped; where done, t =
+        0, epi += 1 and the env's sequence regenerated.  spectrum (float32 [n,
+        A, nf_max, 2] = (sr, si), already scaled) replaces the Philox draws;
+        spec_out (same shape) / peak_out (float32 [n]) receive the regenerated
+        rows' scaled spectra before the masking and their peaks."""
+        self._mask(stepped, "stepped")
+        self._mask(done, "done")
+        self._spec(spectrum, "spectrum")
+        self._spec(spec_out, "spec_out")
+        if peak_out is not None and (tuple(peak_out.shape) != (self.n,) or peak_out.dtype != torch.float32
+                                     or peak_out.device != self.dev or not peak_out.is_contiguous()):
+            raise ValueError(f"PinkNoise.advance: peak_out must be contiguous float32 [{self.n}] on {self.dev}")
+        nat.check(nat.lib().td7f_pink_advance(self.K, self._cseg, self.n, self.A, self.Lmax, len(self.cls_len_host),
+                                              self.cls_len_host, nat.ptr(stepped), nat.ptr(done), nat.ptr(self.t),
+                                              nat.ptr(self.epi), nat.ptr(self.seq), nat.ptr(self.len_cls),
+                                              nat.ptr(self.cls_len), nat.ptr(self.cls_norm), nat.ptr(self.cls_scale),
+                                              self.rows, nat.ptr(self.table), nat.ptr(self.seg_dev),
+                                              nat.ptr(spectrum), nat.ptr(spec_out), nat.ptr(peak_out),
+                                              nat.stream_ptr(self.dev)), "td7f_pink_advance")
+
+
+def select_multi_seq_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, rows, noise_dev,
+                         seg_dev, ticket, seq, t, Lmax, out, scale, npol=None):
+    """td7f_select_multi_seq as it stands in the C ABI; returns its status code."""
+    npol = len(seg) - 1 if npol is None else npol
+    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
+    return nat.lib().td7f_select_multi_seq(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg,
+                                           nat.ptr(tiles_dev), int(ntiles), nat.ptr(obs), int(n), rows,
+                                           nat.ptr(noise_dev), nat.ptr(seg_dev), nat.ptr(ticket), nat.ptr(seq),
+                                           nat.ptr(t), int(Lmax), nat.ptr(out), float(scale),
+                                           nat.stream_ptr(obs.device))
+
+
 class PolicySet:
     """K policies -- (actor, fixed encoder) module pairs of one shape -- packed
     for td7f_select_multi: one launch in which policy p acts on the rows
@@ -900,7 +1003,9 @@ class PolicySet:
         applies); a MultiNoise: every policy its own state
         (td7f_select_multi_noise), times `scale`, and z (float32 [n, A]
         standard normals) then replaces the Philox draws and leaves the
-        counters alone.  Repack changed weights with refresh() first."""
+        counters alone; a PinkNoise: every env column t of its own coloured
+        sequence (td7f_select_multi_seq), times `scale`.  Repack changed
+        weights with refresh() first."""
         key, tiles, nt = self.tiles(seg)
         obs = obs.contiguous()
         n = obs.shape[0]
@@ -919,6 +1024,16 @@ class PolicySet:
             nat.check(select_multi_noise_raw(self.prec, self.act_codes, self.enc, self.actor, self.table, key, tiles,
                                              nt, obs, n, noise.rows, noise.table, self._tiles[key][2], noise.ticket,
                                              z, out, scale), "td7f_select_multi_noise")
+            return out
+        if isinstance(noise, PinkNoise):
+            if noise.K != len(self) or noise.seg != key:
+                raise ValueError(f"PolicySet.act: the PinkNoise was built for {noise.K} policies and seg "
+                                 f"{list(noise.seg)}, not {len(self)} and {list(key)}")
+            if z is not None:
+                raise ValueError("PolicySet.act: z goes with a MultiNoise")
+            nat.check(select_multi_seq_raw(self.prec, self.act_codes, self.enc, self.actor, self.table, key, tiles,
+                                           nt, obs, n, noise.rows, noise.table, noise.seg_dev, noise.ticket,
+                                           noise.seq, noise.t, noise.Lmax, out, scale), "td7f_select_multi_seq")
             return out
         if z is not None:
             raise ValueError("PolicySet.act: z goes with a MultiNoise")

@@ -832,6 +832,64 @@ int td7f_select_multi_noise(int32_t prec, const int32_t *act, int32_t npol, cons
  * and its device copy as `noise_dev`, so that what the host validates is what
  * the kernel reads. */
 int td7f_multi_noise_table(int32_t npol, const td7f_noise *noise, td7f_noise_row *table);
+/* Coloured (power-law) exploration noise with one sequence per env and
+ * asynchronous episodes (TD7_multi_agent_Pink_noise.py:203-228: one sequence
+ * per episode, peak normalised, times the exploration noise at the start of
+ * the episode; column t is added to the action of step t).  One launch after
+ * every env step, over the n envs of td7f_select_multi's layout (seg, seg_dev,
+ * and td7f_select_multi_noise's noise table: key, tag and sigma pointer of each
+ * policy; no call counter is read or written).  For env r of policy p:
+ *   stepped_dev[r] != 0 (uint8 [n]): t_dev[r] += 1;
+ *   done_dev[r] != 0: t_dev[r] = 0, epi_dev[r] += 1 and the [n_r][A] block of
+ *     seq_dev [n][Lmax][A] (fp32; the A values of one step contiguous) is
+ *     regenerated, n_r = cls_len[len_cls_dev[r]].  Columns t >= n_r are never
+ *     written.
+ * Regeneration is the Timmer-Koenig construction in fp32: for column c and
+ * k < nf = n_r / 2 + 1, sr_k = z0 * scale_k and si_k = z1 * scale_k with
+ * scale_k = cls_scale_dev[cls][k] and (z0, z1) the Box-Muller pair of Philox
+ * block j = ((r - seg[p]) * A + c) * nf_max + k, nf_max = Lmax / 2 + 1, of call
+ * epi_dev[r] (the new value) of the stream (seed_p, tag_p) -- segment-local,
+ * so what a policy draws depends neither on its neighbours nor on where its
+ * segment starts.  Then si_0 = 0, sr_0 *= sqrt 2, the same at k = n_r / 2 for
+ * even n_r, and x[t] = cls_norm_dev[cls] * (sr_0 + 2 sum_k (sr_k cos(2 pi k t /
+ * n_r) - si_k sin(2 pi k t / n_r))) with the Nyquist term taken once: a direct
+ * inverse real DFT.  seq[r][t][c] = x * (*sigma_p / peak), peak = max |x| over
+ * the block, *sigma_p as it stands at this launch (gain 0 when peak == 0).
+ * The first fill is this launch with every env flagged done and epi_dev = -1.
+ *
+ * Tables: len_cls_dev int32 [n]; cls_len (host, validated: 2 <= cls_len[c] <=
+ * Lmax) and its device copy cls_len_dev int32 [ncls]; cls_norm_dev fp32 [ncls]
+ * = 1 / (n sigma_n) of pink.py's _spectrum_scale; cls_scale_dev fp32
+ * [ncls][nf_max].  spectrum_dev (may be NULL): given spectra fp32
+ * [n][A][nf_max][2] = (sr, si), already scaled, in place of the draws.
+ * spec_out_dev (may be NULL, same shape): the scaled spectra of the
+ * regenerated rows before the masking.  peak_out_dev (may be NULL) fp32 [n]:
+ * their peak.  A <= 8.  EXO_EINVAL for a NULL or inconsistent argument or a
+ * table that does not fit the LDS, EXO_ERANGE when a policy's rows * A *
+ * nf_max does not fit 32 bits; nothing launched then.  The call allocates
+ * nothing and copies nothing to the device, and td7f_probe makes it validate
+ * and return. */
+int td7f_pink_advance(int32_t npol, const int32_t *seg, int32_t n, int32_t A, int32_t Lmax, int32_t ncls,
+                      const int32_t *cls_len, const uint8_t *stepped_dev, const uint8_t *done_dev, int32_t *t_dev,
+                      int32_t *epi_dev, float *seq_dev, const int32_t *len_cls_dev, const int32_t *cls_len_dev,
+                      const float *cls_norm_dev, const float *cls_scale_dev, const td7f_noise_row *noise,
+                      const void *noise_dev, const int32_t *seg_dev, const float *spectrum_dev, float *spec_out_dev,
+                      float *peak_out_dev, void *stream);
+/* td7f_select_multi with the coloured noise of td7f_pink_advance
+ * (TD7_multi_agent_Pink_noise.py:203-228 per env): row r of policy p, column
+ * c, gets e = seq_dev[r][min(t_dev[r], Lmax - 1)][c], clamped to +-clip_p when
+ * clip_p > 0, and act_out = clamp(a + e, -1, 1) * scale.  The sequence is
+ * already scaled by the sigma of its episode's start.  The last workgroup out
+ * (ticket_dev as in td7f_select_multi_noise) does *sigma_p -= sigma_dec_p for
+ * every policy whose segment is not empty; no Philox counter moves and t_dev
+ * is only read, so two launches without a td7f_pink_advance between them add
+ * the same noise.  Arguments, tables and errors as td7f_select_multi_noise,
+ * without z_dev; a NULL seq_dev or t_dev or Lmax <= 0 is EXO_EINVAL. */
+int td7f_select_multi_seq(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
+                          const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
+                          const float *obs_dev, int32_t n, const td7f_noise_row *noise, const void *noise_dev,
+                          const int32_t *seg_dev, uint32_t *ticket_dev, const float *seq_dev, const int32_t *t_dev,
+                          int32_t Lmax, float *act_out_dev, float scale, void *stream);
 /* The critic target chain (TD7_multi_agent.py:233-241): fixed_target_zs(s'),
  * next_action = actor_target(s', zs) + clipped noise, fixed_target_zsa and both
  * heads of critic_target -> qt_dev [B][2].  tenc: zs1..zs3, zsa1..zsa3;

@@ -17,10 +17,16 @@ per step, run one after the other over the same policies and env counts.  The
 two arms alternate in one process, per precision (bf16, fp32); seconds by a
 host clock around a device synchronise.
 
+--noise pink collects with one coloured noise sequence per env and episode
+(fused.PinkNoise, exponent --beta) instead of white noise.  --bench --noise pink
+times three collectors at one shape, alternating: the pink one, the Gaussian
+one, and ComposedPinkCollector, pink noise from the pieces that need the host
+every step (read done, hipFFT for the finished envs, gather, given normals).
+
 usage: python tools/collect_dataset.py (--dir DIR | --stand-ins K) [--sigma S [S ...]] [--envs-per-policy 64]
-                                       [--steps 500] [--precision fp32] [--out FILE]
+                                       [--steps 500] [--precision fp32] [--noise pink [--beta 1.0]] [--out FILE]
        python tools/collect_dataset.py --bench [--stand-ins 15] [--envs-per-policy 800] [--steps 100]
-                                       [--repeats 5] [--graph] [--out FILE.json]
+                                       [--repeats 5] [--graph] [--noise pink] [--out FILE.json]
 """
 import argparse
 import ctypes
@@ -127,6 +133,88 @@ def bench(a, device):
     return res
 
 
+class ComposedPinkCollector(Collector):
+    """Pink noise per env from the pieces that exist without td7f_pink_advance:
+    each step the host reads `done`, the finished envs' sequences are drawn
+    anew with pink.powerlaw_psd_gaussian_device (torch.randn + hipFFT, one call
+    per motion length among them) and peak-normalised, column t of every env's
+    sequence is gathered into z, and PolicySet.act(noise=MultiNoise, z=z) adds
+    z * sigma.  The host read rules graph replay out; everything else of the
+    step is Collector's."""
+
+    def __init__(self, *args, beta=1.0, **kw):
+        kw["graph"] = False
+        super().__init__(*args, **kw)
+        self.beta = float(beta)
+        self._len = np.asarray(self.env.lengths_host)
+        A = self.policy_set.A
+        self._seq = torch.zeros((self.n, A, int(self._len.max())), dtype=torch.float32, device=self.device)
+        self._t = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        self._rows = torch.arange(self.n, device=self.device)
+        self._last_done = None
+        self._regenerate(np.arange(self.n))
+
+    def _regenerate(self, ids):
+        from exo_amd import pink
+        A = self.policy_set.A
+        for n in np.unique(self._len[ids]):
+            rows = ids[self._len[ids] == n]
+            x = pink.powerlaw_psd_gaussian_device(self.beta, len(rows) * A, int(n), self.device).view(len(rows), A, int(n))
+            x = x / x.abs().amax(dim=(1, 2), keepdim=True)
+            self._seq[torch.as_tensor(rows, device=self.device), :, :int(n)] = x
+
+    def _select(self, obs):
+        if self._last_done is not None:
+            ids = np.flatnonzero(self._last_done.cpu().numpy())  # the host read of every step
+            if ids.size:
+                self._regenerate(ids)
+                self._t[torch.as_tensor(ids, device=self.device)] = 0
+        z = self._seq[self._rows, :, self._t].contiguous()
+        self._t += 1
+        return self.policy_set.act(obs, self.seg, out=self._act, scale=self.max_action, noise=self.noise, z=z)
+
+    def _step(self, c):
+        super()._step(c)
+        self._last_done = self._outs[c][2]
+
+
+def bench_pink(a, device):
+    """--bench --noise pink: the pink Collector, the Gaussian Collector and the
+    composed baseline (ComposedPinkCollector) at one shape, alternating."""
+    pols, activ, env_kw, per_kw = load_policies(a, device)
+    K, n = len(pols), a.envs_per_policy
+    res = dict(policies=K, envs_per_policy=n, steps=a.steps, graph=bool(a.graph), noise="pink", beta=a.beta)
+    for prec in ("bf16", "fp32"):
+        ag, _ = fresh_agent([n] * K, 8, prec, device)  # a ring: the timing does not need every row kept
+        rb = ag.replay_buffer
+        kw = dict(sigma=a.sigma[0], env_kwargs=env_kw, per_policy_env_kwargs=per_kw)
+        cols = dict(pink=Collector(PolicySet(pols, prec, device, activ), [n] * K, rb, graph=a.graph, noise="pink",
+                                   beta=a.beta, **kw),
+                    gaussian=Collector(PolicySet(pols, prec, device, activ), [n] * K, rb, graph=a.graph, **kw),
+                    composed=ComposedPinkCollector(PolicySet(pols, prec, device, activ), [n] * K, rb, beta=a.beta, **kw))
+        for c in cols.values():  # warm-up (and the captures)
+            c.collect(a.steps)
+        t = {k: [] for k in cols}
+        for _ in range(a.repeats):
+            for name, c in cols.items():
+                torch.cuda.synchronize()
+                t0 = time.time()
+                c.collect(a.steps)
+                torch.cuda.synchronize()
+                t[name].append(time.time() - t0)
+        r = res[f"collect_{prec}_s"] = {k: stats(v) for k, v in t.items()}
+        r["transitions"] = K * n * a.steps
+        for k in cols:
+            v = r[k]
+            print(f"{prec:5s} {k:8s} s per {K} x {n} envs x {a.steps} steps: min {v['min']:.4f} median {v['median']:.4f} "
+                  f"max {v['max']:.4f}  ({v['n']})  {r['transitions'] / v['median']:.3g} transitions/s", flush=True)
+        for c in cols.values():
+            c.close()
+        del cols, ag, rb
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     src = ap.add_mutually_exclusive_group()
@@ -140,6 +228,9 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=("bf16", "fp16", "fp32"))
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--graph", action="store_true", help="replay the step from graphs")
+    ap.add_argument("--noise", default="gaussian", choices=("gaussian", "pink"),
+                    help="white Gaussian noise per policy, or one coloured sequence per env and episode")
+    ap.add_argument("--beta", type=float, default=1.0, help="exponent of the coloured noise's power law (1: pink)")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -149,7 +240,7 @@ def main():
         a.stand_ins = a.stand_ins or (None if a.dir else 15)
         a.envs_per_policy = a.envs_per_policy or 800
         a.steps = a.steps or 100
-        line = json.dumps(bench(a, dev))
+        line = json.dumps(bench_pink(a, dev) if a.noise == "pink" else bench(a, dev))
         print(line)
         if a.out:
             with open(a.out, "w") as fh:
@@ -166,7 +257,7 @@ def main():
     ag, _ = fresh_agent([a.envs_per_policy] * K, a.steps, a.precision, dev)
     col = Collector(PolicySet(pols, a.precision, dev, activ), a.envs_per_policy, ag.replay_buffer, sigma=sigma,
                     sigma_dec=a.sigma_dec, clip=a.clip, env_kwargs=env_kw, per_policy_env_kwargs=per_kw, seed=a.seed,
-                    graph=a.graph)
+                    graph=a.graph, noise=a.noise, beta=a.beta)
     try:
         torch.cuda.synchronize()
         t0 = time.time()
@@ -179,7 +270,7 @@ def main():
     if a.out:
         ag.save_dataset(a.out)
     print(json.dumps(dict(policies=K, envs_per_policy=a.envs_per_policy, steps=a.steps, precision=a.precision,
-                          transitions=n, seconds=dt, transitions_per_s=n / dt, out=a.out, per_policy=rep)))
+                          noise=a.noise, transitions=n, seconds=dt, transitions_per_s=n / dt, out=a.out, per_policy=rep)))
 
 
 if __name__ == "__main__":
