@@ -18,6 +18,7 @@
 
 #include "adam_math.h"
 #include "philox.h"
+#include "td7_select.h"
 
 namespace td7f {
 
@@ -301,40 +302,31 @@ __global__ __launch_bounds__(256) void adam_pack_kernel(AdamPackArgs a) {
 // Rows per workgroup = 16 RT.  RT = 1 gives a 4,096-env call one workgroup per
 // CU (fastest alone: the per-CU weight stream bounds the pass); RT = 2 reads
 // each weight half as often and leaves half of the CUs to the graph branches
-// that run beside select_action (EXO_SELECT_RT).  F (the fp32 norm input)
-// overlays H1 | H2, dead whenever F is written.
+// that run beside select_action (EXO_SELECT_RT).
 struct SelectArgs {
-    Lin zs[3], ac[4];
-    int act_enc, act_actor;
-    const float *obs;
-    int n, S, A, Z, Ha;
-    float *out;
-    Noise nz;
-    R16 X, H1, H2, CAT;
-    R32 F, TW, FT;
-    int lds_bytes;
-    int tile0, ticket;  // fp32 chunked launches: first row tile; 1 = take the noise ticket
+    Lin l[7];  // zs1..zs3, l0..l3
+    SelectPlan p;
+    int lds_bytes, tile0, ticket;  // fp32 chunked launches: first row tile; 1 = take the noise ticket
     void *zimg;         // split launches (ZM 1 / 2): the rows' normalised zs in operand type, [n][Z]
+};
+// select_rows' layers from the kernel arguments
+struct ArgLayers {
+    const Lin *l;
+    __device__ __forceinline__ const Lin &operator()(int i) const { return l[i]; }
 };
 
 #define RING_START(first)      \
     Ring<TH> R;                \
     ring_fill<TH>(R, GDesc{(first).wf, (first).ksf, 0})
 
-__device__ __forceinline__ R16 rows_of(R16 r, int t) { return R16{r.off + t * TR * r.ld * 2, r.ld}; }
-__device__ __forceinline__ R32 rows_of(R32 r, int t) { return R32{r.off + t * TR * r.ld * 4, r.ld}; }
-
 // Row tiles tile0 + blockIdx.x: td7f_select may cover the tiles with several
 // launches of at most its workgroup cap each (the same per-row arithmetic and
 // Philox elements); only the last launch takes the noise ticket, so sigma and
 // the call counter advance once, after every tile has drawn.
-// ZM (r06, td7f_select_part): 0 the whole pass; 1 the fixed encoder's zs only,
-// its normalised image stored to a.zimg (no actor, no noise); 2 the actor from
-// that image (the zs layers skipped).  zs needs only the fixed encoder, which
-// changes at target refreshes alone, so a training loop can run the ZM 1 half
-// as soon as the observations exist and only the ZM 2 half after the actor
-// step; the image is the operand-type values ZM 0 leaves in CAT, so 1 + 2 ==
-// 0 bit for bit (same row tiles).
+// ZM (r06, td7f_select_part): select_rows' split modes.  zs needs only the
+// fixed encoder, which changes at target refreshes alone, so a training loop
+// can run the ZM 1 half as soon as the observations exist and only the ZM 2
+// half after the actor step.
 template <int P, int TH, int RT, int ZM = 0>
 __global__ __launch_bounds__(NTH) void select_kernel(SelectArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -344,91 +336,11 @@ __global__ __launch_bounds__(NTH) void select_kernel(SelectArgs a) {
     int row0;
     if constexpr (RT == 1) row0 = (a.tile0 + blockIdx.x) * rows;
     else row0 = blockIdx.x * rows;
-    int si = 0;
-    FSTAMP(si);
-    RowStage so[RT];
-    ThinStage<THIN_NC> tw;
-    using E = typename Ty<P>::E;
-    static_assert(RT * TR * (int)sizeof(E) <= 64, "ZM 2 staging: 16 rows x 512 words at most");
-#pragma unroll
-    for (int t = 0; t < RT; ++t) row_issue(so[t], a.obs, a.S, a.S, row0 + t * TR, a.n);
-    if constexpr (ZM != 1) thin_issue(tw, a.ac[3].w, a.ac[3].ldw, 0, false, a.A, a.ac[3].K);
-    // ZM 2: this workgroup's zs image rows in 4-byte words (Z * EB % 4 == 0,
-    // at most 16 rows x 512 words per 512 threads: checked on the host),
-    // loaded with the observations
-    const int zw = a.Z * (int)sizeof(E) / 4;
-    constexpr int ZPT = ZM == 2 ? (16 * 512 + NTH - 1) / NTH : 1;
-    uint32_t zv[ZPT];
-    if constexpr (ZM == 2) {
-        const uint32_t *zi = (const uint32_t *)a.zimg;
-#pragma unroll
-        for (int u = 0; u < ZPT; ++u) {
-            const int k = threadIdx.x + u * NTH, r = k / zw, c = k - r * zw;
-            zv[u] = (r < rows && row0 + r < a.n) ? zi[(long)(row0 + r) * zw + c] : 0u;
-        }
-    }
-    RING_START(ZM == 2 ? a.ac[0] : a.zs[0]);
-    zero_lds(lds, a.lds_bytes);
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RT; ++t) row_put16<P>(lds, so[t], rows_of(a.X, t), 0, a.S, row0 + t * TR, a.n);
-    if constexpr (ZM != 1) thin_put<P>(lds, tw, a.TW, a.A, a.ac[3].K);
-    if constexpr (ZM == 2) {
-#pragma unroll
-        for (int u = 0; u < ZPT; ++u) {
-            const int k = threadIdx.x + u * NTH, r = k / zw, c = k - r * zw;
-            if (r < rows) *(uint32_t *)(pe<P>(lds, a.CAT, r, a.Ha) + c * (4 / (int)sizeof(E))) = zv[u];
-        }
-    }
-    __syncthreads();
-    if constexpr (ZM != 2) {
-        // zs = fixed_encoder.zs(obs) (:93-97) -> CAT[:, Ha:Ha+Z]
-        layer_fwd<P, RT, TH>(lds, R, a.X, a.zs[0], &a.zs[1], a.act_enc, a.H1, 0, NO32, nullptr, 0, row0, a.n, si);
-        layer_fwd<P, RT, TH>(lds, R, a.H1, a.zs[1], &a.zs[2], a.act_enc, a.H2, 0, NO32, nullptr, 0, row0, a.n, si);
-        layer_fwd<P, RT, TH>(lds, R, a.H2, a.zs[2], ZM == 1 ? (const Lin *)nullptr : &a.ac[0], ACT_NONE, NO16, 0, a.F,
-                             nullptr, 0, row0, a.n, si);
-        norm_fwd<P>(lds, a.F, a.Z, rows, 1e-8f, a.CAT, a.Ha, NO16, 0, NO32, nullptr, 0, nullptr, nullptr, row0, a.n);
-        __syncthreads();
-    }
-    if constexpr (ZM == 1) {
-        uint32_t *zo = (uint32_t *)a.zimg;
-        for (int k = threadIdx.x; k < rows * zw; k += NTH) {
-            const int r = k / zw, c = k - r * zw;
-            if (row0 + r < a.n)
-                zo[(long)(row0 + r) * zw + c] = *(const uint32_t *)(pe<P>(lds, a.CAT, r, a.Ha) + c * (4 / (int)sizeof(E)));
-        }
-        return;
-    }
-    // actor (:72-77): AvgL1Norm(l0(s)) | zs -> l1 -> l2 -> tanh(l3)
-    layer_fwd<P, RT, TH>(lds, R, a.X, a.ac[0], &a.ac[1], ACT_NONE, NO16, 0, a.F, nullptr, 0, row0, a.n, si);
-    norm_fwd<P>(lds, a.F, a.Ha, rows, 1e-8f, a.CAT, 0, NO16, 0, NO32, nullptr, 0, nullptr, nullptr, row0, a.n);
-    __syncthreads();
-    // F overlaid H1 | H2: their zero padding columns (read by the GEMMs below
-    // where the width is not a multiple of 32 PD) are restored before the
-    // epilogues write H1 / H2 (a fast wave's epilogue may start while another
-    // wave still zeroes: the barrier orders them)
-    if (a.F.off == a.H1.off) {
-        zero_lds(lds + a.H1.off, a.H2.off + rows * a.H2.ld * 2 - a.H1.off);
-        __syncthreads();
-    }
-    layer_fwd<P, RT, TH>(lds, R, a.CAT, a.ac[1], &a.ac[2], a.act_actor, a.H1, 0, NO32, nullptr, 0, row0, a.n, si);
-    layer_fwd<P, RT, TH>(lds, R, a.H1, a.ac[2], (const Lin *)nullptr, a.act_actor, a.H2, 0, NO32, nullptr, 0, row0, a.n, si);
-    if constexpr (RT == 1) {
-        layer_thin_fwd<P, THIN_NC>(lds, a.H2, a.ac[3], a.TW, ACT_TANH, a.FT, rows, nullptr, 0, row0, a.n, si);
-    } else {  // thin products per 16-row tile, then bias + tanh over all rows
-        FSTAMP(si);
-#pragma unroll
-        for (int t = 0; t < RT; ++t)
-            thin<P, THIN_NC>(lds, rows_of(a.H2, t), 0, a.ac[3].K, a.TW, a.A, rows_of(a.FT, t), 1.f);
-        __syncthreads();
-        for (int k = threadIdx.x; k < rows * a.A; k += NTH) {
-            const int row = k / a.A, c = k - row * a.A;
-            *p32(lds, a.FT, row, c) = act_fwd(ACT_TANH, *p32(lds, a.FT, row, c) + ldg(a.ac[3].b + c));
-        }
-        __syncthreads();
-    }
-    if constexpr (RT == 1) noise_rows<P>(lds, a.FT, a.A, rows, row0, a.n, a.nz, a.out, NO16, 0, NO16, 0, a.ticket != 0);
-    else noise_rows<P>(lds, a.FT, a.A, rows, row0, a.n, a.nz, a.out, NO16, 0, NO16, 0);
+    select_rows<P, TH, RT, ZM>(lds, a.p, a.lds_bytes, row0, a.p.n, a.zimg, ArgLayers{a.l});
+    if constexpr (ZM == 1) return;
+    if constexpr (RT == 1)
+        noise_rows<P>(lds, a.p.FT, a.p.A, rows, row0, a.p.n, a.p.nz, a.p.out, NO16, 0, NO16, 0, a.ticket != 0);
+    else noise_rows<P>(lds, a.p.FT, a.p.A, rows, row0, a.p.n, a.p.nz, a.p.out, NO16, 0, NO16, 0);
 }
 
 // ---------------------------------------------------------------- critic target chain
@@ -727,27 +639,9 @@ int select_impl(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
     if (!prec_ok(prec) || !act || !enc || !actor || !obs || n <= 0 || wg_cap < 0 || rt < 0 || rt > 2 || zm < 0 ||
         zm > 2 || (zm != 1 && (!noise || !out)) || (zm != 0 && !zimg))
         return EXO_EINVAL;
-    const int kd = kd_of(prec);
     td7f_lin all[7] = {enc[0], enc[1], enc[2], actor[0], actor[1], actor[2], actor[3]};
     const int th = th_of(all, 7);
     if (th != 4 && th != 5) return EXO_EINVAL;
-    SelectArgs a{};
-    for (int i = 0; i < 3; ++i) a.zs[i] = lin_of(enc[i]);
-    for (int i = 0; i < 4; ++i) a.ac[i] = lin_of(actor[i]);
-    a.act_enc = act[0];
-    a.act_actor = act[1];
-    a.obs = obs;
-    a.n = n;
-    a.S = enc[0].n_in;
-    a.A = actor[3].n_out;
-    a.Z = enc[2].n_out;
-    a.Ha = actor[0].n_out;
-    if (actor[0].n_in != a.S || actor[1].n_in != a.Ha + a.Z || a.A > THIN_NC || a.S > NTH) return EXO_EINVAL;
-    a.out = out;
-    if (zm != 1) a.nz = noise_of(*noise);
-    a.zimg = zimg;
-    if (zm != 0 && (((long)a.Z * (prec == PREC_F32 ? 4 : 2)) % 4 || ((long)a.Ha * (prec == PREC_F32 ? 4 : 2)) % 4 || a.Z > 512))
-        return EXO_EINVAL;  // the image moves in 4-byte words, at most 512 per row
     // 32-row tiles above 8,192 envs (more than two 16-row workgroups per CU:
     // the weights are then streamed half as often; configs[3]'s 16,384 envs
     // 0.452 vs 0.494 ms per iteration, profiles/r04q_raw); 16-row tiles below
@@ -761,21 +655,18 @@ int select_impl(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
     const int RT = prec == PREC_F32 ? 1
                    : rt_env && (rt_env[0] == '1' || rt_env[0] == '2') ? rt_env[0] - '0'
                    : rt ? rt : (n > 8192 ? 2 : 1);
-    const int rows = RT * TR, hmax = std::max(enc[0].n_out, std::max(enc[1].n_out, std::max(a.Ha, actor[1].n_out)));
-    Bump b;
-    a.X = b.r16(rows, ld16(a.S, kd));
-    a.H1 = b.r16(rows, ld16(hmax, kd));
-    a.H2 = b.r16(rows, ld16(hmax, kd));
-    const int fld = std::max(std::max(a.Z, a.Ha), 16);
-    if (rows * fld * 4 <= a.H2.off + rows * a.H2.ld * 2 - a.H1.off) {
-        a.F = R32{a.H1.off, fld};  // overlays H1 | H2 (both dead whenever F is written)
-    } else {
-        a.F = b.r32(rows, fld);
-    }
-    a.CAT = b.r16(rows, ld16(a.Ha + a.Z, kd));
-    a.TW = b.r32(THIN_NC, actor[3].n_in);
-    a.FT = b.r32(rows, 16);
-    a.lds_bytes = b.off;
+    SelectArgs a{};
+    for (int i = 0; i < 7; ++i) a.l[i] = lin_of(all[i]);
+    if (select_plan(prec, act, enc, actor, RT * TR, a.p, a.lds_bytes) != EXO_OK) return EXO_EINVAL;
+    a.p.obs = obs;
+    a.p.out = out;
+    a.p.n = n;
+    if (zm != 1) a.p.nz = noise_of(*noise);
+    a.zimg = zimg;
+    const int eb = prec == PREC_F32 ? 4 : 2;
+    if (zm != 0 && (((long)a.p.Z * eb) % 4 || ((long)a.p.Ha * eb) % 4 || a.p.Z > 512))
+        return EXO_EINVAL;  // the image moves in 4-byte words, at most 512 per row
+    const int rows = RT * TR, lds = a.lds_bytes;
     // workgroup cap (wg_cap; EXO_SELECT_WG_CAP overrides it when set; 0 = all
     // tiles in one launch): the tiles in launches of at most cap workgroups back to
     // back, leaving CUs to the fused passes that run beside select_action in
@@ -793,14 +684,14 @@ int select_impl(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
             a.tile0 = t0;
             a.ticket = t0 + cap >= ntiles;
             const dim3 g(std::min(cap, ntiles - t0));
-            const int rc = select_mode(zm, prec, th, 1, g, b.off, a, st);
+            const int rc = select_mode(zm, prec, th, 1, g, lds, a, st);
             if (rc != EXO_OK) return rc;
         }
         return EXO_OK;
     }
     a.tile0 = 0;
     a.ticket = 1;
-    return select_mode(zm, prec, th, RT, dim3(ntiles), b.off, a, st);
+    return select_mode(zm, prec, th, RT, dim3(ntiles), lds, a, st);
 }
 }  // namespace
 

@@ -7,9 +7,9 @@
 //
 // An evaluation of K policies over a few hundred envs each is K launches of a
 // few dozen workgroups on 256 CUs; here the K row ranges are one grid.  The
-// per-row arithmetic is select_kernel's (td7_fused.hip, 16-row tiles), built
-// from the same blocks of td7_fused.h; what differs is where a workgroup gets
-// its work from:
+// per-row arithmetic and the LDS plan are select_kernel's own (select_rows and
+// select_plan of td7_select.h at 16-row tiles, the whole pass); what differs
+// is where a workgroup gets its work from:
 //
 //   tile table   int32 [ntiles][3] = (policy, row0, row_end), indexed by
 //                blockIdx.x.  A tile never straddles a segment (a workgroup
@@ -48,25 +48,19 @@
 //                       td7f_pink_advance (td7_pink.hip) keeps, already scaled
 //                       by sigma; the ticket advances sigma only, no Philox
 //                       counter moves.
-#include "td7_fused.h"
-
 #include <algorithm>
+
+#include "td7_select.h"
 
 namespace td7f {
 
 struct SelectMultiArgs {
     const td7f_lin *pol;  // device [npol][7]
     const int *tiles;     // device [ntiles][3]
-    int act_enc, act_actor;
-    const float *obs;
-    int S, A, Z, Ha;
-    float *out;
-    Noise nz;
-    int noisy;    // 0: deterministic (nz unused, no noise state touched)
-    float scale;  // deterministic mode's max_action
-    R16 X, H1, H2, CAT;
-    R32 F, TW, FT;
+    SelectPlan p;
     int lds_bytes;
+    int noisy;    // 0: deterministic (p.nz unused, no noise state touched)
+    float scale;  // deterministic mode's max_action
 };
 
 // a wave-uniform 32-bit word as a scalar (the compiler folds it when the load
@@ -104,46 +98,12 @@ __device__ __forceinline__ void tile_at(const int *tiles, int &pol, int &row0, i
     rend = (int)uni((uint32_t)ldg(tp + 2));
 }
 
-// select_kernel<P, TH, 1, 0>'s networks on the tile (pol, row0, rend): leaves
-// tanh(l3(...)) of the tile's rows in the fp32 region a.FT.
-template <int P, int TH>
-__device__ __forceinline__ void select_multi_rows(char *lds, const SelectMultiArgs &a, int pol, int row0, int rend) {
-    constexpr int rows = TR;
-    int si = 0;
-    FSTAMP(si);
-    const Lin zs1 = lin_at(a.pol, pol, 0), l3 = lin_at(a.pol, pol, 6);
-    RowStage so;
-    ThinStage<THIN_NC> tw;
-    row_issue(so, a.obs, a.S, a.S, row0, rend);
-    thin_issue(tw, l3.w, l3.ldw, 0, false, a.A, l3.K);
-    Ring<TH> R;
-    ring_fill<TH>(R, GDesc{zs1.wf, zs1.ksf, 0});
-    zero_lds(lds, a.lds_bytes);
-    __syncthreads();
-    row_put16<P>(lds, so, a.X, 0, a.S, row0, rend);
-    thin_put<P>(lds, tw, a.TW, a.A, l3.K);
-    __syncthreads();
-    // zs = fixed_encoder.zs(obs) (:93-97) -> CAT[:, Ha:Ha+Z]
-    const Lin zs2 = lin_at(a.pol, pol, 1), zs3 = lin_at(a.pol, pol, 2), l0 = lin_at(a.pol, pol, 3);
-    layer_fwd<P, 1, TH>(lds, R, a.X, zs1, &zs2, a.act_enc, a.H1, 0, NO32, nullptr, 0, row0, rend, si);
-    layer_fwd<P, 1, TH>(lds, R, a.H1, zs2, &zs3, a.act_enc, a.H2, 0, NO32, nullptr, 0, row0, rend, si);
-    layer_fwd<P, 1, TH>(lds, R, a.H2, zs3, &l0, ACT_NONE, NO16, 0, a.F, nullptr, 0, row0, rend, si);
-    norm_fwd<P>(lds, a.F, a.Z, rows, 1e-8f, a.CAT, a.Ha, NO16, 0, NO32, nullptr, 0, nullptr, nullptr, row0, rend);
-    __syncthreads();
-    // actor (:72-77): AvgL1Norm(l0(s)) | zs -> l1 -> l2 -> tanh(l3)
-    const Lin l1 = lin_at(a.pol, pol, 4), l2 = lin_at(a.pol, pol, 5);
-    layer_fwd<P, 1, TH>(lds, R, a.X, l0, &l1, ACT_NONE, NO16, 0, a.F, nullptr, 0, row0, rend, si);
-    norm_fwd<P>(lds, a.F, a.Ha, rows, 1e-8f, a.CAT, 0, NO16, 0, NO32, nullptr, 0, nullptr, nullptr, row0, rend);
-    __syncthreads();
-    // F overlaid H1 | H2: their zero padding columns restored (see select_kernel)
-    if (a.F.off == a.H1.off) {
-        zero_lds(lds + a.H1.off, a.H2.off + rows * a.H2.ld * 2 - a.H1.off);
-        __syncthreads();
-    }
-    layer_fwd<P, 1, TH>(lds, R, a.CAT, l1, &l2, a.act_actor, a.H1, 0, NO32, nullptr, 0, row0, rend, si);
-    layer_fwd<P, 1, TH>(lds, R, a.H1, l2, (const Lin *)nullptr, a.act_actor, a.H2, 0, NO32, nullptr, 0, row0, rend, si);
-    layer_thin_fwd<P, THIN_NC>(lds, a.H2, l3, a.TW, ACT_TANH, a.FT, rows, nullptr, 0, row0, rend, si);
-}
+// select_rows' layers of policy `pol` from the policy table, loaded when asked for
+struct TableLayers {
+    const td7f_lin *tab;
+    int pol;
+    __device__ __forceinline__ Lin operator()(int i) const { return lin_at(tab, pol, i); }
+};
 
 // select_kernel<P, TH, 1, 0> on the tile (policy, row0, row_end) of blockIdx.x.
 template <int P, int TH>
@@ -152,28 +112,60 @@ __global__ __launch_bounds__(NTH) void select_multi_kernel(SelectMultiArgs a) {
     constexpr int rows = TR;
     int pol, row0, rend;
     tile_at(a.tiles, pol, row0, rend);
-    select_multi_rows<P, TH>(lds, a, pol, row0, rend);
+    select_rows<P, TH, 1, 0>(lds, a.p, a.lds_bytes, row0, rend, nullptr, TableLayers{a.pol, pol});
+    const int A = a.p.A;
     if (a.noisy) {
         // one noise state for the launch: the Philox element is the global
         // row's, the last workgroup out takes the ticket
-        noise_rows<P>(lds, a.FT, a.A, rows, row0, rend, a.nz, a.out, NO16, 0, NO16, 0, true);
+        noise_rows<P>(lds, a.p.FT, A, rows, row0, rend, a.p.nz, a.p.out, NO16, 0, NO16, 0, true);
         return;
     }
-    for (int k = threadIdx.x; k < rows * a.A; k += NTH) {
-        const int row = k / a.A, c = k - row * a.A;
+    for (int k = threadIdx.x; k < rows * A; k += NTH) {
+        const int row = k / A, c = k - row * A;
         if (row0 + row < rend)
-            stg(a.out + (size_t)(row0 + row) * a.A + c, fminf(fmaxf(*p32(lds, a.FT, row, c), -1.0f), 1.0f) * a.scale);
+            stg(a.p.out + (size_t)(row0 + row) * A + c, fminf(fmaxf(*p32(lds, a.p.FT, row, c), -1.0f), 1.0f) * a.scale);
     }
+}
+
+// ---- noise per policy: what td7f_select_multi_noise and td7f_select_multi_seq share
+struct PerPolicyArgs {
+    SelectMultiArgs s;          // s.p.nz / s.noisy unused
+    const td7f_noise_row *nzt;  // device [npol]
+    const int *seg;             // device [npol + 1]
+    uint32_t *ticket;
+    int npol;
+};
+
+// The end of a per-policy launch, called after a barrier that left the LDS
+// images dead and every thread of this workgroup past its reads of its
+// policy's state: the last workgroup out advances the policies that acted
+// (sigma; with `counter` the Philox call counter too), thread k policy k
+// (vector lanes, plain stores).
+__device__ __forceinline__ void advance_policies(char *lds, const PerPolicyArgs &m, bool counter) {
+    int *last = (int *)lds;
+    if (threadIdx.x == 0) {
+        __threadfence();
+        *last = atomicAdd(m.ticket, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!*last) return;
+    for (int k = threadIdx.x; k < m.npol; k += NTH) {
+        if (ldg(m.seg + k + 1) <= ldg(m.seg + k)) continue;
+        const td7f_noise_row *r = m.nzt + k;
+        float *sg = ldg(&r->sigma);
+        *sg = ldg(sg) - ldg(&r->sigma_dec);
+        if (counter) {
+            unsigned long long *cnt = ldg(&r->counter);
+            *cnt = ldg(cnt) + 1ull;
+        }
+    }
+    if (threadIdx.x == 0) *m.ticket = 0u;
 }
 
 // ---- one noise state per policy (td7f_select_multi_noise)
 struct SelectMultiNoiseArgs {
-    SelectMultiArgs s;          // s.nz / s.noisy unused
-    const td7f_noise_row *nzt;  // device [npol]
-    const int *seg;             // device [npol + 1]
-    uint32_t *ticket;
+    PerPolicyArgs pp;
     const float *z;  // given standard normals [n][A] (null: Philox)
-    int npol;
 };
 
 // row `pol` of the noise table as a Noise (td7f_noise_row is 10 words); only
@@ -204,48 +196,27 @@ template <int P, int TH>
 __global__ __launch_bounds__(NTH) void select_multi_noise_kernel(SelectMultiNoiseArgs m) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int rows = TR;
-    const SelectMultiArgs &a = m.s;
+    const SelectMultiArgs &a = m.pp.s;
     int pol, row0, rend;
     tile_at(a.tiles, pol, row0, rend);
-    select_multi_rows<P, TH>(lds, a, pol, row0, rend);
+    select_rows<P, TH, 1, 0>(lds, a.p, a.lds_bytes, row0, rend, nullptr, TableLayers{a.pol, pol});
     // noise_rows as it stands, on the segment as a tensor of its own: with the
     // rows counted from seg0 its element (row * A + c) is the segment-local
     // one, and out / z moved to the segment's first row put it back
-    const int seg0 = (int)uni((uint32_t)ldg(m.seg + pol));
-    const size_t off = (size_t)seg0 * a.A;
-    const Noise nz = noise_at(m.nzt, pol, a.scale, m.z ? m.z + off : nullptr);
-    noise_rows<P>(lds, a.FT, a.A, rows, row0 - seg0, rend - seg0, nz, a.out + off, NO16, 0, NO16, 0, false);
-    // (noise_rows ended with a barrier: every thread of this workgroup has
-    // read its sigma and counter, and the LDS images are dead)
-    int *last = (int *)lds;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        *last = atomicAdd(m.ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!*last) return;
-    // every workgroup has read its policy's state before its ticket: advance
-    // the policies that acted, thread k policy k (vector lanes, plain stores)
-    for (int k = threadIdx.x; k < m.npol; k += NTH) {
-        if (ldg(m.seg + k + 1) <= ldg(m.seg + k)) continue;
-        const td7f_noise_row *r = m.nzt + k;
-        float *sg = ldg(&r->sigma);
-        unsigned long long *cnt = ldg(&r->counter);
-        *sg = ldg(sg) - ldg(&r->sigma_dec);
-        if (!m.z) *cnt = ldg(cnt) + 1ull;
-    }
-    if (threadIdx.x == 0) *m.ticket = 0u;
+    const int seg0 = (int)uni((uint32_t)ldg(m.pp.seg + pol));
+    const size_t off = (size_t)seg0 * a.p.A;
+    const Noise nz = noise_at(m.pp.nzt, pol, a.scale, m.z ? m.z + off : nullptr);
+    noise_rows<P>(lds, a.p.FT, a.p.A, rows, row0 - seg0, rend - seg0, nz, a.p.out + off, NO16, 0, NO16, 0, false);
+    // (noise_rows ended with a barrier, after the reads of sigma and counter)
+    advance_policies(lds, m.pp, !m.z);
 }
 
 // ---- a coloured sequence per env (td7f_select_multi_seq)
 struct SelectMultiSeqArgs {
-    SelectMultiArgs s;          // s.nz / s.noisy unused
-    const td7f_noise_row *nzt;  // device [npol]: sigma, sigma_dec, clip (no Philox state is touched)
-    const int *seg;             // device [npol + 1]
-    uint32_t *ticket;
+    PerPolicyArgs pp;  // of pp.nzt: sigma, sigma_dec, clip (no Philox state is touched)
     const float *seq;  // [n][Lmax][A], td7f_pink_advance's table
     const int *t;      // [n] step index of each env's episode
-    int Lmax, npol;
+    int Lmax;
 };
 
 // noise_rows' sibling for a noise term that is already scaled: global row R =
@@ -272,28 +243,15 @@ template <int P, int TH>
 __global__ __launch_bounds__(NTH) void select_multi_seq_kernel(SelectMultiSeqArgs m) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int rows = TR;
-    const SelectMultiArgs &a = m.s;
+    const SelectMultiArgs &a = m.pp.s;
     int pol, row0, rend;
     tile_at(a.tiles, pol, row0, rend);
-    select_multi_rows<P, TH>(lds, a, pol, row0, rend);
-    const float clip = __uint_as_float(uni(ldg((const uint32_t *)(m.nzt + pol) + 9)));
-    seq_rows(lds, a.FT, a.A, rows, row0, rend, m.seq, m.t, m.Lmax, clip, a.scale, a.out);
-    // (seq_rows ended with a barrier: the LDS images are dead)
-    int *last = (int *)lds;
-    if (threadIdx.x == 0) {
-        __threadfence();
-        *last = atomicAdd(m.ticket, 1u) == gridDim.x - 1;
-    }
-    __syncthreads();
-    if (!*last) return;
-    // sigma is read by td7f_pink_advance only, between launches: thread k policy k
-    for (int k = threadIdx.x; k < m.npol; k += NTH) {
-        if (ldg(m.seg + k + 1) <= ldg(m.seg + k)) continue;
-        const td7f_noise_row *r = m.nzt + k;
-        float *sg = ldg(&r->sigma);
-        *sg = ldg(sg) - ldg(&r->sigma_dec);
-    }
-    if (threadIdx.x == 0) *m.ticket = 0u;
+    select_rows<P, TH, 1, 0>(lds, a.p, a.lds_bytes, row0, rend, nullptr, TableLayers{a.pol, pol});
+    const float clip = __uint_as_float(uni(ldg((const uint32_t *)(m.pp.nzt + pol) + 9)));
+    seq_rows(lds, a.p.FT, a.p.A, rows, row0, rend, m.seq, m.t, m.Lmax, clip, a.scale, a.p.out);
+    // (seq_rows ended with a barrier; sigma is read by td7f_pink_advance only,
+    // between launches)
+    advance_policies(lds, m.pp, false);
 }
 
 }  // namespace td7f
@@ -344,8 +302,8 @@ int td7f_multi_noise_table(int32_t npol, const td7f_noise *noise, td7f_noise_row
 
 }  // extern "C"
 
-// td7f_select_multi's argument checks and LDS plan (select_impl's at RT = 1)
-// into a; th: tiles per wave.  EXO_OK or the error to return.
+// td7f_select_multi's argument checks and LDS plan (select_plan for policy 0
+// at 16 rows) into a; th: tiles per wave.  EXO_OK or the error to return.
 static int multi_plan(int32_t prec, const int32_t *act, int32_t npol, const td7f_lin *enc, const td7f_lin *actor,
                       const void *policies_dev, const int32_t *seg, const int32_t *tiles_dev, int32_t ntiles,
                       const float *obs, int32_t n, float *out, float scale, SelectMultiArgs &a, int &th) {
@@ -360,7 +318,6 @@ static int multi_plan(int32_t prec, const int32_t *act, int32_t npol, const td7f
         nt += (seg[p + 1] - seg[p] + TR - 1) / TR;
     }
     if (nt != ntiles) return EXO_EINVAL;
-    const int kd = kd_of(prec);
     th = 0;
     for (int p = 0; p < npol; ++p) {
         const td7f_lin *e = enc + 3 * (size_t)p, *c = actor + 4 * (size_t)p;
@@ -378,33 +335,28 @@ static int multi_plan(int32_t prec, const int32_t *act, int32_t npol, const td7f
     a = SelectMultiArgs{};
     a.pol = (const td7f_lin *)policies_dev;
     a.tiles = tiles_dev;
-    a.act_enc = act[0];
-    a.act_actor = act[1];
-    a.obs = obs;
-    a.S = enc[0].n_in;
-    a.A = actor[3].n_out;
-    a.Z = enc[2].n_out;
-    a.Ha = actor[0].n_out;
-    if (actor[0].n_in != a.S || actor[1].n_in != a.Ha + a.Z || a.A > THIN_NC || a.S > NTH) return EXO_EINVAL;
-    if ((long)n * a.A >= (1L << 31)) return EXO_ERANGE;  // the Philox element index is 32 bits
-    a.out = out;
+    if (select_plan(prec, act, enc, actor, TR, a.p, a.lds_bytes) != EXO_OK) return EXO_EINVAL;
+    if ((long)n * a.p.A >= (1L << 31)) return EXO_ERANGE;  // the Philox element index is 32 bits
+    a.p.obs = obs;
+    a.p.n = n;
+    a.p.out = out;
     a.scale = scale;
-    // select_impl's plan at RT = 1
-    const int rows = TR, hmax = std::max(enc[0].n_out, std::max(enc[1].n_out, std::max(a.Ha, actor[1].n_out)));
-    Bump b;
-    a.X = b.r16(rows, ld16(a.S, kd));
-    a.H1 = b.r16(rows, ld16(hmax, kd));
-    a.H2 = b.r16(rows, ld16(hmax, kd));
-    const int fld = std::max(std::max(a.Z, a.Ha), 16);
-    if (rows * fld * 4 <= a.H2.off + rows * a.H2.ld * 2 - a.H1.off) {
-        a.F = R32{a.H1.off, fld};  // overlays H1 | H2 (both dead whenever F is written)
-    } else {
-        a.F = b.r32(rows, fld);
+    return EXO_OK;
+}
+
+// ... and, after them, a per-policy launch's: the host image of the noise
+// table (`counter`: a policy that acts needs a Philox call counter) into m
+static int per_policy_plan(int32_t npol, const int32_t *seg, const td7f_noise_row *noise, const void *noise_dev,
+                           const int32_t *seg_dev, uint32_t *ticket_dev, bool counter, PerPolicyArgs &m) {
+    if (!noise || !noise_dev || !seg_dev || !ticket_dev) return EXO_EINVAL;
+    for (int p = 0; p < npol; ++p) {
+        if (!(noise[p].sigma_dec >= 0.f) || !(noise[p].clip >= 0.f)) return EXO_EINVAL;
+        if (seg[p + 1] > seg[p] && (!noise[p].sigma || (counter && !noise[p].counter))) return EXO_EINVAL;
     }
-    a.CAT = b.r16(rows, ld16(a.Ha + a.Z, kd));
-    a.TW = b.r32(THIN_NC, actor[3].n_in);
-    a.FT = b.r32(rows, 16);
-    a.lds_bytes = b.off;
+    m.nzt = (const td7f_noise_row *)noise_dev;
+    m.seg = seg_dev;
+    m.ticket = ticket_dev;
+    m.npol = npol;
     return EXO_OK;
 }
 
@@ -419,7 +371,7 @@ int td7f_select_multi(int32_t prec, const int32_t *act, int32_t npol, const td7f
                               a, th);
     if (rc != EXO_OK) return rc;
     a.noisy = noise != nullptr;
-    if (noise) a.nz = noise_of(*noise);
+    if (noise) a.p.nz = noise_of(*noise);
     return DISPATCH(prec, th, select_multi_kernel, dim3((unsigned)ntiles), a.lds_bytes, a, (hipStream_t)stream);
 }
 
@@ -430,20 +382,12 @@ int td7f_select_multi_noise(int32_t prec, const int32_t *act, int32_t npol, cons
                             uint32_t *ticket_dev, const float *z_dev, float *out, float scale, void *stream) {
     SelectMultiNoiseArgs m{};
     int th;
-    const int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
-                              m.s, th);
+    int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
+                        m.pp.s, th);
+    if (rc == EXO_OK) rc = per_policy_plan(npol, seg, noise, noise_dev, seg_dev, ticket_dev, true, m.pp);
     if (rc != EXO_OK) return rc;
-    if (!noise || !noise_dev || !seg_dev || !ticket_dev) return EXO_EINVAL;
-    for (int p = 0; p < npol; ++p) {
-        if (!(noise[p].sigma_dec >= 0.f) || !(noise[p].clip >= 0.f)) return EXO_EINVAL;
-        if (seg[p + 1] > seg[p] && (!noise[p].sigma || !noise[p].counter)) return EXO_EINVAL;
-    }
-    m.nzt = (const td7f_noise_row *)noise_dev;
-    m.seg = seg_dev;
-    m.ticket = ticket_dev;
     m.z = z_dev;
-    m.npol = npol;
-    return DISPATCH(prec, th, select_multi_noise_kernel, dim3((unsigned)ntiles), m.s.lds_bytes, m,
+    return DISPATCH(prec, th, select_multi_noise_kernel, dim3((unsigned)ntiles), m.pp.s.lds_bytes, m,
                     (hipStream_t)stream);
 }
 
@@ -454,22 +398,15 @@ int td7f_select_multi_seq(int32_t prec, const int32_t *act, int32_t npol, const 
                           int32_t Lmax, float *out, float scale, void *stream) {
     SelectMultiSeqArgs m{};
     int th;
-    const int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
-                              m.s, th);
+    int rc = multi_plan(prec, act, npol, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, out, scale,
+                        m.pp.s, th);
+    if (rc == EXO_OK) rc = per_policy_plan(npol, seg, noise, noise_dev, seg_dev, ticket_dev, false, m.pp);
     if (rc != EXO_OK) return rc;
-    if (!noise || !noise_dev || !seg_dev || !ticket_dev || !seq_dev || !t_dev || Lmax <= 0) return EXO_EINVAL;
-    for (int p = 0; p < npol; ++p) {
-        if (!(noise[p].sigma_dec >= 0.f) || !(noise[p].clip >= 0.f)) return EXO_EINVAL;
-        if (seg[p + 1] > seg[p] && !noise[p].sigma) return EXO_EINVAL;
-    }
-    m.nzt = (const td7f_noise_row *)noise_dev;
-    m.seg = seg_dev;
-    m.ticket = ticket_dev;
+    if (!seq_dev || !t_dev || Lmax <= 0) return EXO_EINVAL;
     m.seq = seq_dev;
     m.t = t_dev;
     m.Lmax = Lmax;
-    m.npol = npol;
-    return DISPATCH(prec, th, select_multi_seq_kernel, dim3((unsigned)ntiles), m.s.lds_bytes, m,
+    return DISPATCH(prec, th, select_multi_seq_kernel, dim3((unsigned)ntiles), m.pp.s.lds_bytes, m,
                     (hipStream_t)stream);
 }
 

@@ -659,17 +659,23 @@ def multi_tiles(seg, rows=16):
     return np.stack([pol, row0, np.minimum(row0 + rows, s[1:][pol])], axis=1).astype(np.int32).reshape(-1, 3)
 
 
+def _select_multi_call(fn, prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, middle, out, scale,
+                       npol):
+    """fn: one of the td7f_select_multi* entry points, which share their first
+    eleven and last three arguments; middle: the ones between."""
+    npol = len(seg) - 1 if npol is None else npol
+    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
+    return fn(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg, nat.ptr(tiles_dev), int(ntiles), nat.ptr(obs),
+              int(n), *middle, nat.ptr(out), float(scale), nat.stream_ptr(obs.device))
+
+
 def select_multi_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, noise, out, scale,
                      npol=None):
     """td7f_select_multi as it stands in the C ABI; returns its status code.
     enc / actor: TD7FLin arrays of 3 / 4 entries per policy; seg: a python
     sequence of npol + 1 ints; noise: a TD7FNoise or None (deterministic)."""
-    npol = len(seg) - 1 if npol is None else npol
-    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
-    return nat.lib().td7f_select_multi(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg, nat.ptr(tiles_dev),
-                                       int(ntiles), nat.ptr(obs), int(n),
-                                       ctypes.byref(noise) if noise is not None else None, nat.ptr(out),
-                                       float(scale), nat.stream_ptr(obs.device))
+    return _select_multi_call(nat.lib().td7f_select_multi, prec, act, enc, actor, policies_dev, seg, tiles_dev,
+                              ntiles, obs, n, (ctypes.byref(noise) if noise is not None else None,), out, scale, npol)
 
 
 def per_policy(value, K, name, owner="MultiNoise"):
@@ -762,12 +768,9 @@ def select_multi_noise_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, 
     """td7f_select_multi_noise as it stands in the C ABI; returns its status
     code.  rows: the host TD7FNoiseRow array (or None), noise_dev / seg_dev /
     ticket / z: device tensors (or None)."""
-    npol = len(seg) - 1 if npol is None else npol
-    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
-    return nat.lib().td7f_select_multi_noise(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg,
-                                             nat.ptr(tiles_dev), int(ntiles), nat.ptr(obs), int(n), rows,
-                                             nat.ptr(noise_dev), nat.ptr(seg_dev), nat.ptr(ticket), nat.ptr(z),
-                                             nat.ptr(out), float(scale), nat.stream_ptr(obs.device))
+    middle = (rows, nat.ptr(noise_dev), nat.ptr(seg_dev), nat.ptr(ticket), nat.ptr(z))
+    return _select_multi_call(nat.lib().td7f_select_multi_noise, prec, act, enc, actor, policies_dev, seg, tiles_dev,
+                              ntiles, obs, n, middle, out, scale, npol)
 
 
 class PinkNoise:
@@ -864,13 +867,9 @@ class PinkNoise:
 def select_multi_seq_raw(prec, act, enc, actor, policies_dev, seg, tiles_dev, ntiles, obs, n, rows, noise_dev,
                          seg_dev, ticket, seq, t, Lmax, out, scale, npol=None):
     """td7f_select_multi_seq as it stands in the C ABI; returns its status code."""
-    npol = len(seg) - 1 if npol is None else npol
-    cseg = (ctypes.c_int32 * len(seg))(*[int(v) for v in seg])
-    return nat.lib().td7f_select_multi_seq(prec, act, npol, enc, actor, nat.ptr(policies_dev), cseg,
-                                           nat.ptr(tiles_dev), int(ntiles), nat.ptr(obs), int(n), rows,
-                                           nat.ptr(noise_dev), nat.ptr(seg_dev), nat.ptr(ticket), nat.ptr(seq),
-                                           nat.ptr(t), int(Lmax), nat.ptr(out), float(scale),
-                                           nat.stream_ptr(obs.device))
+    middle = (rows, nat.ptr(noise_dev), nat.ptr(seg_dev), nat.ptr(ticket), nat.ptr(seq), nat.ptr(t), int(Lmax))
+    return _select_multi_call(nat.lib().td7f_select_multi_seq, prec, act, enc, actor, policies_dev, seg, tiles_dev,
+                              ntiles, obs, n, middle, out, scale, npol)
 
 
 class PolicySet:
