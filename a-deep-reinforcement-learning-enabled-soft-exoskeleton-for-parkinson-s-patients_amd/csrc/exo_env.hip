@@ -1123,6 +1123,26 @@ int exo_episode_advance(exo_ctx *c, uint8_t *active_dev, int32_t *count_dev, int
     return check(c, e, "exo_episode_advance");
 }
 
+namespace {
+// exo_episode_advance's reset list as a mask: mask[e] = 1 for the ids[0 .. ids[n])
+__global__ __launch_bounds__(1024) void reset_mask_kernel(const int32_t *ids, int n, uint8_t *mask) {
+    for (int e = threadIdx.x; e < n; e += blockDim.x) mask[e] = 0;
+    __syncthreads();
+    const int nres = min(max(ids[n], 0), n);
+    for (int i = threadIdx.x; i < nres; i += blockDim.x) {
+        const int e = ids[i];
+        if (e >= 0 && e < n) mask[e] = 1;
+    }
+}
+} // namespace
+
+int exo_reset_mask(exo_ctx *c, const int32_t *reset_ws_dev, uint8_t *mask_dev, void *stream) {
+    if (!c || !reset_ws_dev || !mask_dev) return EXO_EINVAL;
+    DeviceGuard g(c->device);
+    hipLaunchKernelGGL(reset_mask_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, reset_ws_dev, c->N, mask_dev);
+    return check(c, hipGetLastError(), "exo_reset_mask");
+}
+
 int exo_step_carry(exo_ctx *c, const float *act_dev, float *obs_dev, float *rew_dev, uint8_t *done_dev,
                    float *info_dev, const uint8_t *active_dev, const float *obs_cur_dev, void *stream) {
     if (!c || !act_dev || !obs_dev || !rew_dev || !done_dev) return EXO_EINVAL;

@@ -343,6 +343,59 @@ __global__ __launch_bounds__(NTH) void select_kernel(SelectArgs a) {
     else noise_rows<P>(lds, a.p.FT, a.p.A, rows, row0, a.p.n, a.p.nz, a.p.out, NO16, 0, NO16, 0);
 }
 
+// td7f_select_seq: select_kernel's rows with a coloured noise sequence per env
+// (TD7_multi_agent_Pink_noise.py:203-228) in place of the Gaussian draw: row r
+// adds column t[r] of its own row of td7f_pink_advance's table (seq_rows).  Of
+// s.p.nz it reads sigma_dec, clip, scale and the ticket word; the last
+// workgroup out of the launch that takes the ticket does *sigma -= sigma_dec,
+// once per call (:225) -- no Philox counter is read or moved, seq and t are
+// only read.  SelectArgs stays as select_kernel has it (its layout is
+// measured); what this kernel adds follows it.
+struct SelectSeqArgs {
+    SelectArgs s;
+    const float *seq;  // [n][Lmax][A]
+    const int *t;      // [n] step index of each env's episode
+    int Lmax;
+};
+
+template <int P, int TH, int RT, int ZM = 0>
+__global__ __launch_bounds__(NTH) void select_seq_kernel(SelectSeqArgs m) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    static_assert(ZM != 1, "the zs half needs no noise: select_kernel<.., 1>");
+    constexpr int rows = RT * TR;
+    const SelectArgs &a = m.s;
+    int row0;
+    if constexpr (RT == 1) row0 = (a.tile0 + blockIdx.x) * rows;
+    else row0 = blockIdx.x * rows;
+    select_rows<P, TH, RT, ZM>(lds, a.p, a.lds_bytes, row0, a.p.n, a.zimg, ArgLayers{a.l});
+    // the tail's arguments are read from the kernel arguments here, not at the
+    // kernel's start: held in scalar registers through select_rows they cost
+    // the 32-row and ZM 2 instances scalar spills select_kernel does not have
+    // (m is the kernel's one argument: the kernel-argument segment is its
+    // image; the empty asm keeps the loads below it)
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const SelectSeqArgs __attribute__((address_space(4))) *ArgPtr;
+    ArgPtr q = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(q));
+#else
+    const SelectSeqArgs *q = &m;
+#endif
+    const R32 ft{q->s.p.FT.off, q->s.p.FT.ld};
+    seq_rows(lds, ft, q->s.p.A, rows, row0, q->s.p.n, q->seq, q->t, q->Lmax, q->s.p.nz.clip, q->s.p.nz.scale,
+             q->s.p.out);
+    bool ticket = true;
+    if constexpr (RT == 1) ticket = q->s.ticket != 0;
+    if (ticket && threadIdx.x == 0) {
+        __threadfence();
+        uint32_t *const tk = q->s.p.nz.ticket;
+        if (atomicAdd(tk, 1u) == gridDim.x - 1) {
+            float *const sg = q->s.p.nz.sigma;
+            *sg = ldg(sg) - q->s.p.nz.sigma_dec;
+            *tk = 0u;
+        }
+    }
+}
+
 // ---------------------------------------------------------------- critic target chain
 struct TargetArgs {
     Lin enc[6], ac[4], cr[8];
@@ -610,24 +663,42 @@ int td7f_probe(int32_t on) {
 }  // extern "C"
 
 namespace {
-// the select kernel of (precision, weight-tile count, row tiles, split mode)
-template <int ZM>
-int select_one(int prec, int th, int RT, dim3 g, int lds, const SelectArgs &a, hipStream_t st) {
-    using namespace td7f;
-    if (prec == PREC_F32)
-        return th == 5 ? launch(select_kernel<PREC_F32, 5, 1, ZM>, g, lds, a, st)
-                       : launch(select_kernel<PREC_F32, 4, 1, ZM>, g, lds, a, st);
-    if (RT == 2)
-        return prec == PREC_BF16 ? (th == 5 ? launch(select_kernel<PREC_BF16, 5, 2, ZM>, g, lds, a, st)
-                                            : launch(select_kernel<PREC_BF16, 4, 2, ZM>, g, lds, a, st))
-                                 : (th == 5 ? launch(select_kernel<PREC_F16, 5, 2, ZM>, g, lds, a, st)
-                                            : launch(select_kernel<PREC_F16, 4, 2, ZM>, g, lds, a, st));
-    return prec == PREC_BF16 ? (th == 5 ? launch(select_kernel<PREC_BF16, 5, 1, ZM>, g, lds, a, st)
-                                        : launch(select_kernel<PREC_BF16, 4, 1, ZM>, g, lds, a, st))
-                             : (th == 5 ? launch(select_kernel<PREC_F16, 5, 1, ZM>, g, lds, a, st)
-                                        : launch(select_kernel<PREC_F16, 4, 1, ZM>, g, lds, a, st));
-}
-int select_mode(int zm, int prec, int th, int RT, dim3 g, int lds, const SelectArgs &a, hipStream_t st) {
+// the select kernel of (precision, weight-tile count, row tiles, split mode),
+// for select_kernel and for select_seq_kernel
+#define SELECT_ONE(NAME, KERNEL, ARGS)                                                                  \
+    template <int ZM>                                                                                   \
+    int NAME(int prec, int th, int RT, dim3 g, int lds, const ARGS &a, hipStream_t st) {                \
+        using namespace td7f;                                                                           \
+        if (prec == PREC_F32)                                                                           \
+            return th == 5 ? launch(KERNEL<PREC_F32, 5, 1, ZM>, g, lds, a, st)                          \
+                           : launch(KERNEL<PREC_F32, 4, 1, ZM>, g, lds, a, st);                         \
+        if (RT == 2)                                                                                    \
+            return prec == PREC_BF16 ? (th == 5 ? launch(KERNEL<PREC_BF16, 5, 2, ZM>, g, lds, a, st)    \
+                                                : launch(KERNEL<PREC_BF16, 4, 2, ZM>, g, lds, a, st))   \
+                                     : (th == 5 ? launch(KERNEL<PREC_F16, 5, 2, ZM>, g, lds, a, st)     \
+                                                : launch(KERNEL<PREC_F16, 4, 2, ZM>, g, lds, a, st));   \
+        return prec == PREC_BF16 ? (th == 5 ? launch(KERNEL<PREC_BF16, 5, 1, ZM>, g, lds, a, st)        \
+                                            : launch(KERNEL<PREC_BF16, 4, 1, ZM>, g, lds, a, st))       \
+                                 : (th == 5 ? launch(KERNEL<PREC_F16, 5, 1, ZM>, g, lds, a, st)         \
+                                            : launch(KERNEL<PREC_F16, 4, 1, ZM>, g, lds, a, st));       \
+    }
+SELECT_ONE(select_one, select_kernel, SelectArgs)
+SELECT_ONE(select_seq_one, select_seq_kernel, SelectSeqArgs)
+#undef SELECT_ONE
+
+// the coloured sequences of a td7f_select_seq call (null: Gaussian noise)
+struct SeqTail {
+    const float *seq;
+    const int *t;
+    int Lmax;
+};
+
+int select_mode(int zm, int prec, int th, int RT, dim3 g, int lds, const SelectArgs &a, const SeqTail *q,
+                hipStream_t st) {
+    if (q) {
+        const SelectSeqArgs m{a, q->seq, q->t, q->Lmax};
+        return zm == 2 ? select_seq_one<2>(prec, th, RT, g, lds, m, st) : select_seq_one<0>(prec, th, RT, g, lds, m, st);
+    }
     return zm == 1 ? select_one<1>(prec, th, RT, g, lds, a, st)
          : zm == 2 ? select_one<2>(prec, th, RT, g, lds, a, st)
                    : select_one<0>(prec, th, RT, g, lds, a, st);
@@ -635,10 +706,13 @@ int select_mode(int zm, int prec, int th, int RT, dim3 g, int lds, const SelectA
 
 int select_impl(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor, const float *obs,
                 int32_t n, const td7f_noise *noise, float *out, int32_t wg_cap, int32_t rt, void *zimg, int zm,
-                void *stream) {
+                const SeqTail *q, void *stream) {
     if (!prec_ok(prec) || !act || !enc || !actor || !obs || n <= 0 || wg_cap < 0 || rt < 0 || rt > 2 || zm < 0 ||
         zm > 2 || (zm != 1 && (!noise || !out)) || (zm != 0 && !zimg))
         return EXO_EINVAL;
+    // a coloured sequence per env: no zs half (it takes no noise), the table and
+    // the state the ticket's holder writes
+    if (q && (zm == 1 || !q->seq || !q->t || q->Lmax <= 0 || !noise->sigma || !noise->ticket)) return EXO_EINVAL;
     td7f_lin all[7] = {enc[0], enc[1], enc[2], actor[0], actor[1], actor[2], actor[3]};
     const int th = th_of(all, 7);
     if (th != 4 && th != 5) return EXO_EINVAL;
@@ -684,14 +758,14 @@ int select_impl(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
             a.tile0 = t0;
             a.ticket = t0 + cap >= ntiles;
             const dim3 g(std::min(cap, ntiles - t0));
-            const int rc = select_mode(zm, prec, th, 1, g, lds, a, st);
+            const int rc = select_mode(zm, prec, th, 1, g, lds, a, q, st);
             if (rc != EXO_OK) return rc;
         }
         return EXO_OK;
     }
     a.tile0 = 0;
     a.ticket = 1;
-    return select_mode(zm, prec, th, RT, dim3(ntiles), lds, a, st);
+    return select_mode(zm, prec, th, RT, dim3(ntiles), lds, a, q, st);
 }
 }  // namespace
 
@@ -699,14 +773,22 @@ extern "C" {
 
 int td7f_select(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor, const float *obs,
                 int32_t n, const td7f_noise *noise, float *out, int32_t wg_cap, int32_t rt, void *stream) {
-    return select_impl(prec, act, enc, actor, obs, n, noise, out, wg_cap, rt, nullptr, 0, stream);
+    return select_impl(prec, act, enc, actor, obs, n, noise, out, wg_cap, rt, nullptr, 0, nullptr, stream);
 }
 
 int td7f_select_part(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor, const float *obs,
                      int32_t n, const td7f_noise *noise, float *out, int32_t wg_cap, int32_t rt, void *zimg,
                      int32_t mode, void *stream) {
     if (mode != 1 && mode != 2) return EXO_EINVAL;
-    return select_impl(prec, act, enc, actor, obs, n, noise, out, wg_cap, rt, zimg, mode, stream);
+    return select_impl(prec, act, enc, actor, obs, n, noise, out, wg_cap, rt, zimg, mode, nullptr, stream);
+}
+
+int td7f_select_seq(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor, const float *obs,
+                    int32_t n, const td7f_noise *noise, const float *seq, const int32_t *t, int32_t Lmax, float *out,
+                    int32_t wg_cap, int32_t rt, void *zimg, int32_t mode, void *stream) {
+    if (mode != 0 && mode != 2) return EXO_EINVAL;
+    const SeqTail q{seq, t, Lmax};
+    return select_impl(prec, act, enc, actor, obs, n, noise, out, wg_cap, rt, zimg, mode, &q, stream);
 }
 
 int td7f_target(int32_t prec, const int32_t *act, const td7f_lin *tenc, const td7f_lin *tactor,

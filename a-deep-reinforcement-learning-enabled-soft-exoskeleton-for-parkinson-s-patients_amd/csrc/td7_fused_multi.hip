@@ -219,26 +219,9 @@ struct SelectMultiSeqArgs {
     int Lmax;
 };
 
-// noise_rows' sibling for a noise term that is already scaled: global row R =
-// row0 + row of the fp32 actions a gets e = seq[R][min(t[R], Lmax - 1)][c],
-// clamped to +-clip when clip > 0; out = clamp(a + e, -1, 1) * scale.  Ends
-// with a barrier, no ticket.
-__device__ __forceinline__ void seq_rows(char *lds, R32 a, int A, int rows, int row0, int rend, const float *seq,
-                                         const int *t, int Lmax, float clip, float scale, float *out) {
-    for (int k = threadIdx.x; k < rows * A; k += NTH) {
-        const int row = k / A, c = k - row * A, R = row0 + row;
-        if (R < rend) {
-            const int tt = min(max(ldg(t + R), 0), Lmax - 1);
-            float e = ldg(seq + ((size_t)R * Lmax + tt) * A + c);
-            if (clip > 0.f) e = fminf(fmaxf(e, -clip), clip);
-            stg(out + (size_t)R * A + c, fminf(fmaxf(*p32(lds, a, row, c) + e, -1.0f), 1.0f) * scale);
-        }
-    }
-    __syncthreads();
-}
-
 // select_multi_kernel's rows plus each env's own column of its coloured
-// sequence; the last workgroup out advances sigma of the policies with rows.
+// sequence (seq_rows, td7_select.h); the last workgroup out advances sigma of
+// the policies with rows.
 template <int P, int TH>
 __global__ __launch_bounds__(NTH) void select_multi_seq_kernel(SelectMultiSeqArgs m) {
     extern __shared__ __attribute__((aligned(16))) char lds[];

@@ -137,6 +137,25 @@ __device__ __forceinline__ void select_rows(char *lds, const SelectPlan a, int l
     }
 }
 
+// noise_rows' sibling for a noise term that is already scaled (a coloured
+// sequence per env: td7f_select_seq, td7f_select_multi_seq): global row R =
+// row0 + row of the fp32 actions a gets e = seq[R][min(t[R], Lmax - 1)][c],
+// clamped to +-clip when clip > 0; out = clamp(a + e, -1, 1) * scale.  Ends
+// with a barrier, no ticket.
+__device__ __forceinline__ void seq_rows(char *lds, R32 a, int A, int rows, int row0, int rend, const float *seq,
+                                         const int *t, int Lmax, float clip, float scale, float *out) {
+    for (int k = threadIdx.x; k < rows * A; k += NTH) {
+        const int row = k / A, c = k - row * A, R = row0 + row;
+        if (R < rend) {
+            const int tt = min(max(ldg(t + R), 0), Lmax - 1);
+            float e = ldg(seq + ((size_t)R * Lmax + tt) * A + c);
+            if (clip > 0.f) e = fminf(fmaxf(e, -clip), clip);
+            stg(out + (size_t)R * A + c, fminf(fmaxf(*p32(lds, a, row, c) + e, -1.0f), 1.0f) * scale);
+        }
+    }
+    __syncthreads();
+}
+
 // The shape checks and the LDS plan of a select launch with `rows` rows per
 // workgroup (obs, n, out and nz are the caller's); lds_bytes: the images' size.
 // EXO_OK or EXO_EINVAL.

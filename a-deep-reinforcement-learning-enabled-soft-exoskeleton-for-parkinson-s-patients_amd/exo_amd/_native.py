@@ -123,6 +123,7 @@ EXPORTS = {
     "exo_step_carry": (c_int32, [c_void_p] * 9),
     "exo_budget_advance": (c_int32, [c_void_p] * 6),
     "exo_episode_advance": (c_int32, [c_void_p] * 7),
+    "exo_reset_mask": (c_int32, [c_void_p] * 4),
     "exo_multibody_default_params": (None, [P(ExoMbParams)]),
     "exo_set_physics": (c_int32, [c_void_p, c_int32, P(ExoMbParams)]),
     "exo_multibody_advance": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -243,6 +244,9 @@ EXPORTS = {
                               c_int32, c_int32, c_void_p]),
     "td7f_select_part": (c_int32, [c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), c_void_p, c_int32, P(TD7FNoise),
                                    c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "td7f_select_seq": (c_int32, [c_int32, P(c_int32), P(TD7FLin), P(TD7FLin), c_void_p, c_int32, P(TD7FNoise),
+                                  c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int32,
+                                  c_void_p]),
     "td7f_select_multi": (c_int32, [c_int32, P(c_int32), c_int32, P(TD7FLin), P(TD7FLin), c_void_p, P(c_int32),
                                     c_void_p, c_int32, c_void_p, c_int32, P(TD7FNoise), c_void_p, ctypes.c_float,
                                     c_void_p]),

@@ -338,18 +338,35 @@ class FusedNets:
         return img
 
     @torch.no_grad()
-    def select(self, obs, scale=1.0, dec_count=None, world=1, wg_cap=None, rt=None, zs_img=None):
+    def select(self, obs, scale=1.0, dec_count=None, world=1, wg_cap=None, rt=None, zs_img=None, pink=None):
         """select_action_batch with Gaussian exploration (one launch): actor(obs,
         fixed_encoder.zs(obs)) + N(0, exploration_noise) per element, clamped,
         times max_action; exploration_noise decreases once per env (dec_count:
         an int32 device scalar -- once per env counted there, the active envs
         of a vectorised step; times `world`, the data-parallel ranks stepping
-        as many envs each)."""
+        as many envs each).  pink (a PinkNoise.for_learner of these n envs):
+        instead of the Gaussian draw, row r adds column t[r] of its own
+        coloured sequence (td7f_select_seq, still one launch; with zs_img its
+        mode 2) and the noise state the PinkNoise is bound to decreases once
+        per call (TD7_multi_agent_Pink_noise.py:218-226); dec_count and world
+        do not apply."""
         L = self.L
         self.refresh(*(("actor",) if zs_img is not None else ("fixed_encoder", "actor")))
         obs = obs.contiguous()
         n = obs.shape[0]
         out = torch.empty((n, L.actor.l3.out_features), dtype=torch.float32, device=obs.device)
+        if pink is not None:
+            if pink.K != 1 or pink.n != n or pink.A != out.shape[1] or pink.dev != obs.device:
+                raise ValueError(f"FusedNets.select: the PinkNoise holds {pink.K} policies, {pink.n} envs of "
+                                 f"{pink.A} actions on {pink.dev}; the call has 1, {n}, {out.shape[1]} on {obs.device}")
+            nz = pink.noise(scale)
+            fe = self.nets["fixed_encoder"].layers
+            nat.check(nat.lib().td7f_select_seq(self.prec, self.act, _lin_array(fe[:3]), self.nets["actor"].array,
+                                                nat.ptr(obs), n, ctypes.byref(nz), nat.ptr(pink.seq), nat.ptr(pink.t),
+                                                pink.Lmax, nat.ptr(out), int(wg_cap or 0), int(rt or 0),
+                                                nat.ptr(zs_img), 2 if zs_img is not None else 0,
+                                                nat.stream_ptr(obs.device)), "td7f_select_seq")
+            return out
         dec = L.action_noise_decrease * world
         if dec_count is not None:
             nz = self._noise(L._explore_rng, L.exploration_noise_t, dec, 0.0, scale, dec_count=dec_count)
@@ -697,6 +714,34 @@ def per_policy(value, K, name, owner="MultiNoise"):
 # sit next to it), so no policy shares a stream with them or with another
 # policy of the set.
 MULTI_NOISE_TAG0 = 0x4D4E0000
+# ... and the stream a learner's own PinkNoise draws from (PinkNoise.for_learner):
+# outside the MULTI_NOISE_TAG0 + p and + 0x8000 + p ranges and the small tags
+LEARNER_PINK_TAG = 0x504B0000
+
+
+class _OnePolicy:
+    """What PinkNoise and MultiNoise read of a PolicySet, for one learner with
+    no set: one policy whose rows are all n envs."""
+
+    def __init__(self, dev, A, n):
+        self.dev, self.A, self.n = dev, A, int(n)
+        self._seg_dev = torch.tensor([0, self.n], dtype=torch.int32).to(dev)
+
+    def __len__(self):
+        return 1
+
+    def _key(self, seg):
+        key = tuple(int(v) for v in seg)
+        if key != (0, self.n):
+            raise ValueError(f"PinkNoise.for_learner: seg is [0, {self.n}]")
+        return key
+
+    def tiles(self, seg):
+        return self._key(seg), None, -(-self.n // 16)
+
+    def seg_dev(self, seg):
+        self._key(seg)
+        return self._seg_dev
 
 
 class MultiNoise:
@@ -791,12 +836,13 @@ class PinkNoise:
     MultiNoise of the same set).  Row r draws from its policy's stream at call
     epi[r], the index of its episode; the streams' call counters stay 0."""
 
-    def __init__(self, policy_set, seg, lengths, sigma, sigma_dec=0.0, clip=0.0, beta=1.0, tags=None):
+    def __init__(self, policy_set, seg, lengths, sigma, sigma_dec=0.0, clip=0.0, beta=1.0, tags=None, states=None):
         from . import pink
         K = len(policy_set)
         if tags is None:
             tags = [MULTI_NOISE_TAG0 + 0x8000 + p for p in range(K)]
-        self.multi = MultiNoise(policy_set, sigma, sigma_dec, clip, tags=tags)
+        # states: MultiNoise's [(rng, sigma tensor), ...] bound instead of owned (for_learner)
+        self.multi = MultiNoise(policy_set, sigma, sigma_dec, clip, tags=tags, states=states)
         self.K, self.dev, self.A = K, policy_set.dev, policy_set.A
         self.table, self.rows, self.ticket = self.multi.table, self.multi.rows, self.multi.ticket
         self.sigma, self.rngs = self.multi.sigma, self.multi.rngs
@@ -824,6 +870,31 @@ class PinkNoise:
         self.epi = torch.full((n,), -1, dtype=torch.int32, device=d)
         ones = torch.ones((n,), dtype=torch.bool, device=d)
         self.advance(ones, ones)
+
+    @classmethod
+    def for_learner(cls, fused_nets, lengths, clip=0.0, beta=None, tag=LEARNER_PINK_TAG, sigma=None):
+        """The sequences of one learner's envs, for FusedNets.select(pink=...)
+        (td7f_select_seq) -- no PolicySet: one policy, seg = [0, n].  sigma is
+        the learner's own exploration_noise_t, bound (sigma=: another float32
+        device scalar to bind instead), so Gaussian and pink calls move one
+        schedule; sigma_dec its action_noise_decrease (one decrement per
+        call, :225); beta defaults to hp.beta.  The rows draw from a DeviceRNG
+        of this object's own (tag): they draw at call index epi[r], which in
+        the learner's exploration stream would be a Gaussian call's index."""
+        L = fused_nets.L
+        n = len(lengths)
+        layout = _OnePolicy(fused_nets.dev, L.actor.l3.out_features, n)
+        rng = ops.DeviceRNG(fused_nets.dev, int(tag))
+        sig = L.exploration_noise_t if sigma is None else sigma
+        return cls(layout, [0, n], lengths, None, L.action_noise_decrease, clip,
+                   beta=L.hp.beta if beta is None else beta, states=[(rng, sig)])
+
+    def noise(self, scale=1.0):
+        """policy 0's state as the td7f_noise of a td7f_select_seq call: sigma,
+        sigma_dec, clip, this object's ticket word (no Philox state is used)"""
+        r = self.rngs[0]
+        return TD7FNoise(r.seed, r.tag, 0, r.counter_ptr, self.ticket.data_ptr(), self.multi.sigmas[0].data_ptr(),
+                         self.multi.sigma_dec[0], self.multi.clip[0], float(scale), 0, None, None)
 
     def sigma_now(self):
         return self.multi.sigma_now()

@@ -274,8 +274,10 @@ class VecTrainer:
         self.last_actions = None
         # exploration: "gaussian" (TD7_multi_agent.py select_action) or "pink"
         # (TD7_multi_agent_Pink_noise.py: one coloured sequence per episode round)
-        if exploration not in ("gaussian", "pink"):
-            raise ValueError(f"exploration must be 'gaussian' or 'pink', not {exploration!r}")
+        # or "pink_env" (the same noise with one sequence per env and episode:
+        # async episodes, below)
+        if exploration not in ("gaussian", "pink", "pink_env"):
+            raise ValueError(f"exploration must be 'gaussian', 'pink' or 'pink_env', not {exploration!r}")
         self.exploration = exploration
         self.k_dev = torch.zeros((1,), dtype=torch.int64, device=self.device)
         # budgeted env steps (env.set_step_budget, BASELINE configs[3]): a stiff
@@ -309,6 +311,27 @@ class VecTrainer:
                 self._steps_total = torch.zeros((1,), dtype=torch.int64, device=self.device)
         if exploration == "pink":
             agent.init_episode_noise_device(self.round_len)
+        # "pink_env": every env adds column t of its own coloured sequence, of
+        # its own motion's length, regenerated on the device in the iteration
+        # that resets it (fused.PinkNoise: td7f_select_seq in place of the
+        # Gaussian select, one td7f_pink_advance launch after the env step on
+        # the rollout's stream).  Built here, before any capture: its tables,
+        # the first fill and the masks the captured launches read.
+        self.pink = None
+        if exploration == "pink_env":
+            if episodes != "async":
+                raise ValueError("exploration='pink_env' keeps a noise sequence per env and episode: it needs "
+                                 "episodes='async' (synchronous rounds: exploration='pink')")
+            if self.dp:
+                raise ValueError("exploration='pink_env' is not available under data parallelism")
+            if agent.learner.fused is None or self.device.type != "cuda":
+                raise ValueError("exploration='pink_env' needs a learner with the fused passes on the GPU")
+            from .fused import PinkNoise
+            self.pink = PinkNoise.for_learner(agent.learner.fused, Ls)
+            # the envs that consumed an action in the iteration's launch, and
+            # the envs it reset (step budget: not the step's `done`, see _rollout)
+            self._pink_stepped = torch.ones(self.n, dtype=torch.bool, device=self.device)
+            self._pink_done = torch.zeros(self.n, dtype=torch.bool, device=self.device)
         if use_graphs and os.environ.get("EXO_GRAPH_CHECK", "1") != "0":
             graph_reductions_ok(self.device)
 
@@ -354,7 +377,8 @@ class VecTrainer:
     def _split_select_ok(self):
         L = self.agent.learner
         on = self.split_select == "1" or (self.split_select == "auto" and L.precision == "fp32")
-        return on and L.fused is not None and self.exploration == "gaussian" and self.obs.is_cuda
+        # ("pink_env": the actor half is td7f_select_seq's mode 2 from the same zs image)
+        return on and L.fused is not None and self.exploration in ("gaussian", "pink_env") and self.obs.is_cuda
 
     def _select_zs(self):
         """the zs half of this iteration's select_action (see split_select;
@@ -368,7 +392,7 @@ class VecTrainer:
         obs = self.obs
         act = ag.select_action_batch(obs, timestep=self.k_dev if self.exploration == "pink" else None,
                                      dec_count=self.active_count, wg_cap=self._select_cap(), rt=self._select_rt(),
-                                     zs_img=zs_img)
+                                     zs_img=zs_img, pink=self.pink)
         if self._overlap_wait is not None and PAIR_CRITIC_AFTER_SELECT:
             self._select_done = torch.cuda.Event()
             self._select_done.record(torch.cuda.current_stream(self.device))
@@ -378,7 +402,23 @@ class VecTrainer:
         if self._early_on:  # the tree is current from here (see EARLY_LAP)
             self._ins_ev = torch.cuda.Event()
             self._ins_ev.record(torch.cuda.current_stream(self.device))
-        self._advance()
+        if self.pink is None:
+            self._advance()
+        elif not self.budget:
+            # every env stepped (no pending solves: the mask stays all set) and
+            # exo_episode_advance resets exactly the envs whose step was `done`
+            self.pink.advance(self.active, done)
+            self._advance()
+        else:
+            # step budget: `done` is raised by the launch that consumes the
+            # episode's last action, but the env is reset only once that step's
+            # carried solve is complete, maybe launches later (in which `done`
+            # is not rewritten): the mask comes from the advance's reset list.
+            # The launch's own mask is kept before the advance rewrites it.
+            self._pink_stepped.copy_(self.active)
+            self._advance()
+            self.env.reset_mask(self._pink_done)
+            self.pink.advance(self._pink_stepped, self._pink_done)
         self.last_actions = act
 
     def _advance(self, rew=None, score=None):

@@ -1477,7 +1477,7 @@ class Agent:
 
     @torch.no_grad()
     def select_action_batch(self, obs, use_checkpoint=False, use_exploration=True, timestep=None, dec_count=None,
-                            wg_cap=None, rt=None, zs_img=None):
+                            wg_cap=None, rt=None, zs_img=None, pink=None):
         """Device-resident batched actions for the vectorised loop (no host sync).
         timestep (int64 device tensor [1]): Pink-noise exploration -- column
         `timestep` of the episode's noise (init_episode_noise_device) is added
@@ -1489,8 +1489,18 @@ class Agent:
         envs, and every rank's replica takes all of their decrements) -- dec_count
         (int32 device scalar): one per env counted there, the envs still
         running at this step of a synchronous round (the script calls
-        select_action only for envs that are not done, :125-128)."""
+        select_action only for envs that are not done, :125-128).
+        pink (a fused.PinkNoise.for_learner of these envs): Pink-noise
+        exploration with one sequence per env -- row r adds column t[r] of its
+        own sequence, for envs whose episodes start and end on their own --
+        in the fused launch (FusedNets.select(pink=)); one decrement per
+        call.  The caller advances it (PinkNoise.advance) after the env step."""
         fz = self.learner.fused
+        if pink is not None:
+            if fz is None or use_checkpoint or not use_exploration or timestep is not None or not obs.is_cuda:
+                raise ValueError("select_action_batch: pink= needs the fused exploration path on the GPU "
+                                 "(no use_checkpoint, no timestep)")
+            return fz.select(obs, scale=self.max_action, wg_cap=wg_cap, rt=rt, zs_img=zs_img, pink=pink)
         if fz is not None and use_exploration and timestep is None and not use_checkpoint and obs.is_cuda:
             # zs, actor and the noise in one launch
             return fz.select(obs, scale=self.max_action, dec_count=dec_count, world=self.sync.world, wg_cap=wg_cap,

@@ -182,6 +182,19 @@ class VecExoskeletonEnv:
                                                 nat.ptr(steps_total), nat.ptr(obs_out), self._stream()),
                   "exo_episode_advance", self._ctx)
 
+    def reset_mask(self, mask):
+        """The envs the last episode_advance reset (exo_reset_mask) into mask
+        (bool / uint8 [N]): with a step budget an env is reset only once its
+        final step's solve is complete, launches after the step's `done`."""
+        if getattr(self, "_reset_ws", None) is None:
+            raise RuntimeError("reset_mask: no episode_advance has run")
+        if mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("reset_mask: mask must be bool or uint8")
+        self._check_out(mask, (self.n,), mask.dtype)
+        nat.check(nat.lib().exo_reset_mask(self._ctx, nat.ptr(self._reset_ws), nat.ptr(mask), self._stream()),
+                  "exo_reset_mask", self._ctx)
+        return mask
+
     def new_outputs(self, with_info=True):
         d = self.device
         return (torch.empty((self.n, OBS_DIM), dtype=torch.float32, device=d),

@@ -160,6 +160,13 @@ int exo_budget_advance(exo_ctx *ctx, uint8_t *active_dev, int32_t *count_dev, in
  * 111-113) with a per-env one, as a vectorised env's auto-reset. */
 int exo_episode_advance(exo_ctx *c, uint8_t *active_dev, int32_t *count_dev, int32_t *reset_ws_dev,
                         int64_t *steps_total_dev, float *obs_dev, void *stream);
+/* The envs exo_episode_advance just reset, as a mask: mask_dev[e] (uint8 [N])
+ * = 1 for the envs listed in reset_ws_dev, 0 elsewhere.  With a step budget
+ * an env is reset launches after its done step (once that step's solve is
+ * complete), so the step's `done` output does not say when; per-env state
+ * kept beside the envs (a coloured-noise sequence per episode,
+ * TD7_multi_agent_Pink_noise.py:203-207) follows this mask. */
+int exo_reset_mask(exo_ctx *c, const int32_t *reset_ws_dev, uint8_t *mask_dev, void *stream);
 
 /* Step clock (measurement; no reference counterpart): with clock_dev non-NULL
  * (3 device uint64), every later exo_step -- eager or captured into a graph --
@@ -731,6 +738,26 @@ int td7f_select(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7
 int td7f_select_part(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor,
                      const float *obs_dev, int32_t n, const td7f_noise *noise, float *act_out_dev, int32_t wg_cap,
                      int32_t rt, void *zs_img_dev, int32_t mode, void *stream);
+/* td7f_select with a coloured (pink) noise sequence per env in place of the
+ * Gaussian draw (TD7_multi_agent_Pink_noise.py:203-228, with asynchronous
+ * episodes): the same rows, LDS plan, rt and wg_cap as td7f_select; row r adds
+ * e = seq_dev[r][clamp(t_dev[r], 0, Lmax - 1)][c] (seq_dev [n][Lmax][A],
+ * already scaled by the exploration noise of the episode's start, and t_dev
+ * [n] are td7f_pink_advance's tables, only read here), clamped to +-clip when
+ * clip > 0: act_out = clamp(a + e, -1, 1) * scale.  Of `noise` it uses sigma,
+ * sigma_dec, clip, scale and the ticket word: the last workgroup out of the
+ * (last) launch does *sigma -= sigma_dec once per call (:225); no Philox
+ * counter is read or moved and dec_count is ignored.  mode 0: one pass; mode
+ * 2: the actor half from the zs image td7f_select_part(mode 1) wrote (mode 1
+ * takes no noise, so that entry serves it; 1 then 2 == 0 bit for bit at the
+ * same rt).  EXO_EINVAL, nothing launched, for td7f_select's cases, a null
+ * seq_dev or t_dev, Lmax <= 0, any other mode and mode 2 without an image.
+ * Nothing is allocated or copied to the device: the call can be captured in
+ * a graph. */
+int td7f_select_seq(int32_t prec, const int32_t *act, const td7f_lin *enc, const td7f_lin *actor,
+                    const float *obs_dev, int32_t n, const td7f_noise *noise, const float *seq_dev,
+                    const int32_t *t_dev, int32_t Lmax, float *act_out_dev, int32_t wg_cap, int32_t rt,
+                    void *zs_img_dev, int32_t mode, void *stream);
 /* select_action of npol policies in one launch (csrc/td7_fused_multi.hip;
  * TD7_multi_agent.py:192-209 / TD7_multi_agent_Pink_noise.py:212-214 per
  * policy): policy p -- fixed encoder zs1..zs3 at enc[3p..3p+2], actor l0..l3
