@@ -489,18 +489,24 @@ constexpr int THIN_NC = 8;  // action width <= 8 (7 here); the Q heads use 1
 // the loss gradients): dP = dy act'(Y) (Y from global fp32 y[(row0+row)*yld + n]
 // when act != ACT_NONE), rows >= nrows zero; written as the 16-bit image (x gs,
 // columns 0..N), its fp32 column sums part[n] and (fp32) back into dy.
+// A column's 16 values are read before the first store: the stores go to LDS
+// too, and a read after one would wait for it (the regions are distinct, which
+// the compiler cannot know).
 template <int P>
 __device__ __forceinline__ void make_dp(char *lds, R32 dy, int N, int act, const float *y, long yld, R16 o16,
                                         float *part, int row0, int nrows) {
     for (int n = threadIdx.x; n < N; n += NTH) {
+        float v[TR];
+#pragma unroll
+        for (int r = 0; r < TR; ++r) v[r] = *p32(lds, dy, r, n);
         float cs = 0.f;
+#pragma unroll
         for (int r = 0; r < TR; ++r) {
-            float v = *p32(lds, dy, r, n);
-            if (row0 + r >= nrows) v = 0.f;
-            else if (act != ACT_NONE) v *= act_grad(act, ldg(y + (long)(row0 + r) * yld + n));
-            *p32(lds, dy, r, n) = v;
-            *pe<P>(lds, o16, r, n) = Ty<P>::bits(v * Ty<P>::gs);
-            cs += v;
+            if (row0 + r >= nrows) v[r] = 0.f;
+            else if (act != ACT_NONE) v[r] *= act_grad(act, ldg(y + (long)(row0 + r) * yld + n));
+            *p32(lds, dy, r, n) = v[r];
+            *pe<P>(lds, o16, r, n) = Ty<P>::bits(v[r] * Ty<P>::gs);
+            cs += v[r];
         }
         if (part) stg(part + n, cs);
     }
@@ -698,55 +704,83 @@ __device__ __forceinline__ void norm_fwd(char *lds, R32 h, int N, int rows, floa
     }
 }
 
+// Two separately rounded products and their difference, and a product added
+// to +0: never contracted to a multiply-add, which would round differently
+// (norm_bwd's element; td7_fused_train.hip layer_bwd_rank1's accumulator).
+__device__ __forceinline__ float mul_sub_mul(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    const float ab = a * b, cd = c * d;
+    return ab - cd;
+}
+__device__ __forceinline__ float zero_plus_mul(float a, float b) {
+#pragma clang fp contract(off)
+    const float ab = a * b;
+    return 0.f + ab;
+}
+
 // AvgL1Norm backward (td7_ops.hip avgl1_bwd_kernel) of dy (fp32 LDS [16][N])
 // given the pre-norm h (fp32 LDS) and the row means; the result is the layer's
 // gradient operand dP (no activation before a norm): 16-bit LDS image (x gs),
-// dP^T in HBM and the bias-gradient column partials.  16 rows.
+// dP^T in HBM and the bias-gradient column partials; dy is overwritten with
+// the fp32 dP.  16 rows.
+// The 32 threads of a row take its dot product (the butterfly leaves the same
+// sum in every lane), each works out the row's two scalars once -- 1 / m and
+// dot / (m^2 N), two IEEE divisions -- and they write the row's elements, every
+// thread the columns it read for the dot: no barrier in between.  The column
+// sums and the transposed stores (a thread per column, rows in order) follow a
+// barrier, when the caller wants either.
 template <int P>
-__device__ __forceinline__ void norm_bwd(char *lds, R32 dy, R32 h, const float *mean, int N, float eps, float *dot,
-                                         R16 o16, void *dpt, long dpt_ld, float *part, int row0, int nrows) {
+__device__ __forceinline__ void norm_bwd(char *lds, R32 dy, R32 h, const float *mean, int N, float eps, R16 o16,
+                                         void *dpt, long dpt_ld, float *part, int row0, int nrows) {
     {
         constexpr int tpr = NTH / TR;
         const int row = threadIdx.x / tpr, j0 = threadIdx.x % tpr;
         float acc = 0.f;
         for (int n = j0; n < N; n += tpr) acc += *p32(lds, dy, row, n) * *p32(lds, h, row, n);
         for (int o = tpr / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-        if (j0 == 0) dot[row] = acc;
+        const float m = mean[row];
+        const bool big = m >= eps, live = row0 + row < nrows;
+        float inv = 0.f, c = 0.f;
+        if (big) {
+            inv = 1.0f / m;
+            c = acc * inv * inv / N;
+        }
+        for (int n = j0; n < N; n += tpr) {
+            const float d = *p32(lds, dy, row, n);
+            float gx;
+            if (big) {
+                const float xv = *p32(lds, h, row, n);
+                const float sg = (xv > 0.f) ? 1.f : ((xv < 0.f) ? -1.f : 0.f);
+                gx = mul_sub_mul(d, inv, sg, c);
+            } else {
+                gx = d / eps;
+            }
+            if (!live) gx = 0.f;
+            *p32(lds, dy, row, n) = gx;
+            *pe<P>(lds, o16, row, n) = Ty<P>::bits(gx * Ty<P>::gs);
+        }
     }
+    if (!dpt && !part) return;  // (kernel-uniform)
     __syncthreads();
     for (int n = threadIdx.x; n < N; n += NTH) {
-        float csum = 0.f;
-        uint32_t v[8];
-        float f[TR];
+        float g[TR];
 #pragma unroll
-        for (int r = 0; r < TR; ++r) {
-            const float m = mean[r];
-            float gx;
-            if (m >= eps) {
-                const float inv = 1.0f / m, c = dot[r] * inv * inv / N;
-                const float xv = *p32(lds, h, r, n);
-                const float sg = (xv > 0.f) ? 1.f : ((xv < 0.f) ? -1.f : 0.f);
-                gx = *p32(lds, dy, r, n) * inv - sg * c;
-            } else {
-                gx = *p32(lds, dy, r, n) / eps;
-            }
-            if (row0 + r >= nrows) gx = 0.f;
-            csum += gx;
-            const auto hb = Ty<P>::bits(gx * Ty<P>::gs);
-            *pe<P>(lds, o16, r, n) = hb;
-            if constexpr (P == PREC_F32) {
-                f[r] = hb;
-            } else {
-                if (r & 1) v[r >> 1] |= (uint32_t)hb << 16;
-                else v[r >> 1] = hb;
-            }
-        }
+        for (int r = 0; r < TR; ++r) g[r] = *p32(lds, dy, r, n);
+        float csum = 0.f;
+#pragma unroll
+        for (int r = 0; r < TR; ++r) csum += g[r];
         if (dpt) {
             if constexpr (P == PREC_F32) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    stg((floatx4 *)blk4((float *)dpt, dpt_ld, n, row0 + 4 * q), floatx4{f[4 * q], f[4 * q + 1], f[4 * q + 2], f[4 * q + 3]});
+                    stg((floatx4 *)blk4((float *)dpt, dpt_ld, n, row0 + 4 * q),
+                        floatx4{Ty<P>::bits(g[4 * q] * Ty<P>::gs), Ty<P>::bits(g[4 * q + 1] * Ty<P>::gs),
+                                Ty<P>::bits(g[4 * q + 2] * Ty<P>::gs), Ty<P>::bits(g[4 * q + 3] * Ty<P>::gs)});
             } else {
+                uint32_t v[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    v[q] = (uint32_t)Ty<P>::bits(g[2 * q] * Ty<P>::gs) | ((uint32_t)Ty<P>::bits(g[2 * q + 1] * Ty<P>::gs) << 16);
                 stg((u32x4 *)blk8((uint16_t *)dpt, dpt_ld, n, row0), u32x4{v[0], v[1], v[2], v[3]});
                 stg((u32x4 *)blk8((uint16_t *)dpt, dpt_ld, n, row0 + 8), u32x4{v[4], v[5], v[6], v[7]});
             }

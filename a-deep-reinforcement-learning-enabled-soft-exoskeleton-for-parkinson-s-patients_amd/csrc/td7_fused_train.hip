@@ -57,6 +57,33 @@ __device__ __forceinline__ void layer_bwd(char *lds, Ring<TH> &R, R16 a, const L
     __syncthreads();
 }
 
+// dX of a one-output layer (the Q heads) from its dP image a (column 0):
+// dX[row][n] = dP[row] w[n], a rank-1 product, on the VALU in the gemm's
+// accumulator layout -- as a GEMM it would stream a whole layer's worth of
+// packed zeros.  w: the head's weights as thin_put left them in LDS (rounded
+// to the operand type, wl row 0, n < c1).  One product per element, added to
+// +0 as the MFMA's chain starts: the gemm's bits.  The epilogue is layer_bwd's.
+// Ends with a barrier.
+template <int P, int TH>
+__device__ __forceinline__ void layer_bwd_rank1(char *lds, R16 a, R32 wl, int c1, int act, const float *y, long yld,
+                                                R16 o16, float *part, int row0, int nrows, int &si) {
+    FSTAMP(si);
+    floatx4 acc[1][os_of(TH)], yv[1][os_of(TH)];
+    epi_prefetch<1, TH>(EpiSrc{act != ACT_NONE ? y : nullptr, yld, 0, row0, nrows, c1}, 0, yv);
+    const float x = Ty<P>::val(*pe<P>(lds, a, acc_row(0), 0));
+#pragma unroll
+    for (int j = 0; j < os_of(TH); ++j) {
+        const int i = own_slot<TH>(j), col = acc_col(0, i);
+        floatx4 w{0.f, 0.f, 0.f, 0.f};
+        if (i < TH && col < c1) w = *(const floatx4 *)p32(lds, wl, 0, col);  // (c1 % 4 == 0)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[0][j][e] = zero_plus_mul(x, w[e]);
+    }
+    FSTAMP(si);
+    epi_bwd<P, 1, TH>(lds, acc, 0, 0, c1, act, yv, NO32, nullptr, 0, o16, part, row0, nrows);
+    __syncthreads();
+}
+
 __device__ __forceinline__ GDesc fwd_of(const Lin &L) { return GDesc{L.wf, L.ksf, 0}; }
 __device__ __forceinline__ GDesc bwd_of(const Lin &L, int c0) { return GDesc{L.wb, L.ksb, c0 / 16}; }
 
@@ -84,7 +111,7 @@ struct CriticArgs {
     long ld;           // row stride of the transposed operands
     R16 X, CAT, H1, H2, DP0, DP1;
     R32 H0, DY, F, TW;
-    int small_off;     // 2 x 16 floats: row means, row dots
+    int small_off;     // 16 floats: row means
     int lds_bytes;
     // phase (td7f_critic_phase): 0 the whole pass; 1 the forward alone, its
     // state for the backward stored -- Q [2][Bp], the pre-norm q0 output H0
@@ -100,15 +127,31 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     const int row0 = blockIdx.x * TR, B = a.B, h = blockIdx.y, Hc = a.Hc, Z = a.Z, tile = blockIdx.x;
     const Lin *cr = a.cr + h;  // layer l of head h: cr[2 l]
     const XT *xt = a.xt + h;
-    float *mean = (float *)(lds + a.small_off), *dot = mean + TR;
+    float *mean = (float *)(lds + a.small_off);
     float *y1 = a.y1 + (long)h * B * Hc, *y2 = a.y2 + (long)h * B * Hc;
     int si = 0;
     FSTAMP(si);
     Ring<TH> R;
     const long Bp = (long)gridDim.x * TR;
+    // the loss block's operands of row threadIdx.x % 16 and q3's bias, loaded
+    // with the kernel-start batch (in mid-kernel each is a cold round trip all
+    // 8 waves wait for) but behind the ring's loads, so that the first barrier's
+    // wait for the input rows does not cover them; addresses clamped, values
+    // masked at use.  (Phase 1 has no loss, and its qt is still being written.)
+    float l_q0 = 0.f, l_q1 = 0.f, l_rw = 0.f, l_nd = 0.f, l_lo = 0.f, l_hi = 0.f, l_b3 = 0.f;
+    const auto loss_issue = [&] {
+        const int lb = min(row0 + (int)(threadIdx.x % TR), B - 1);
+        if (a.phase != 1) {
+            l_q0 = ldg(a.qt + 2 * lb), l_q1 = ldg(a.qt + 2 * lb + 1);
+            l_rw = ldg(a.reward + lb), l_nd = ldg(a.not_done + lb);
+            l_lo = ldg(a.lo), l_hi = ldg(a.hi);
+        }
+        l_b3 = ldg(cr[6].b);
+    };
     if (a.phase == 2) {
-        // the forward's state back into LDS (the same fp32 values), the ring
-        // filled with q3's first backward k-steps as the forward's tail left it
+        // the forward's state back into LDS (the same fp32 values), q3's
+        // weights for its rank-1 dX, the ring filled with q2's first backward
+        // k-steps as the forward's tail left it
         constexpr int PER = TR * 320 / NTH;  // H0 values per thread (Hc <= 320)
         const float *h0 = a.h0s + ((long)h * Bp + row0) * Hc;
         float v[PER];
@@ -119,7 +162,10 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
         }
         const float qv = threadIdx.x < TR ? ldg(a.qs + h * Bp + row0 + threadIdx.x) : 0.f;
         const float mv = threadIdx.x < TR ? ldg(a.ms + h * Bp + row0 + threadIdx.x) : 0.f;
-        ring_fill<TH>(R, bwd_of(cr[6], 0));
+        ThinStage<1> tw;
+        thin_issue(tw, cr[6].w, cr[6].ldw, 0, false, 1, cr[6].K);
+        ring_fill<TH>(R, bwd_of(cr[4], 0));
+        loss_issue();
         zero_lds(lds, a.lds_bytes);
         __syncthreads();
 #pragma unroll
@@ -131,6 +177,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
             *p32(lds, a.F, threadIdx.x, 0) = qv;
             mean[threadIdx.x] = mv;
         }
+        thin_put<P>(lds, tw, a.TW, 1, cr[6].K);
         __syncthreads();
     } else {
     RowStage ss, sa, sz, szs;
@@ -141,6 +188,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     row_issue(szs, a.zs, Z, Z, row0, B);
     thin_issue(tw, cr[6].w, cr[6].ldw, 0, false, 1, cr[6].K);
     ring_fill<TH>(R, fwd_of(cr[0]));
+    loss_issue();
     zero_lds(lds, a.lds_bytes);
     __syncthreads();
     row_put16<P>(lds, ss, a.X, 0, a.S, row0, B);
@@ -156,11 +204,16 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     save_xt<P>(lds, a.X, 0, a.S + a.A, xt[0].x, a.ld, TR, row0);
     save_xt<P>(lds, a.CAT, 0, Hc + 2 * Z, xt[2].x, a.ld, TR, row0);
     layer_fwd<P, 1, TH>(lds, R, a.CAT, cr[2], &cr[4], a.act, a.H1, 0, NO32, y1, Hc, row0, B, si);
-    const GDesc b3 = bwd_of(cr[6], 0);
-    layer_fwd<P, 1, TH>(lds, R, a.H1, cr[4], &b3, a.act, a.H2, 0, NO32, y2, Hc, row0, B, si);
+    // (q3's dX is a rank-1 product on the VALU: the next GEMM is q2's dX)
+    const GDesc b2 = bwd_of(cr[4], 0);
+    layer_fwd<P, 1, TH>(lds, R, a.H1, cr[4], &b2, a.act, a.H2, 0, NO32, y2, Hc, row0, B, si);
     save_xt<P>(lds, a.H1, 0, Hc, xt[4].x, a.ld, TR, row0);
     save_xt<P>(lds, a.H2, 0, Hc, xt[6].x, a.ld, TR, row0);
-    layer_thin_fwd<P, 1>(lds, a.H2, cr[6], a.TW, ACT_NONE, a.F, TR, nullptr, 0, row0, B, si);
+    // q3 (thin) + its bias; the thread of a row goes on to the row's loss
+    FSTAMP(si);
+    thin<P, 1>(lds, a.H2, 0, cr[6].K, a.TW, 1, a.F, 1.f);
+    __syncthreads();
+    if (threadIdx.x < TR) *p32(lds, a.F, threadIdx.x, 0) += l_b3;
     if (a.phase == 1) {  // the state the backward launch needs, then done
         __syncthreads();
         float *h0 = a.h0s + ((long)h * Bp + row0) * Hc;
@@ -178,9 +231,9 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
         float dq = 0.f;
         if (b < B) {
             const float qv = *p32(lds, a.F, r, 0);
-            const float qm = fminf(ldg(a.qt + 2 * b), ldg(a.qt + 2 * b + 1));
-            const float c = fminf(fmaxf(qm, ldg(a.lo)), ldg(a.hi));
-            const float t = ldg(a.reward + b) + (ldg(a.not_done + b) * a.discount) * c;
+            const float qm = fminf(l_q0, l_q1);
+            const float c = fminf(fmaxf(qm, l_lo), l_hi);
+            const float t = l_rw + (l_nd * a.discount) * c;
             if (h == 0) {
                 atomic_max_f(a.run_max, t);
                 atomic_min_f(a.run_min, t);
@@ -198,9 +251,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     make_dp<P>(lds, a.F, 1, ACT_NONE, nullptr, 0, a.DP1, xt[6].part + (long)tile * 1, row0, B);
     __syncthreads();
     save_xt<P>(lds, a.DP1, 0, 1, xt[6].dp, a.ld, TR, row0);
-    const GDesc nx1 = bwd_of(cr[4], 0);
-    layer_bwd<P, TH>(lds, R, a.DP1, cr[6], 0, Hc, &nx1, a.act, y2, Hc, NO32, nullptr, 0, a.DP0,
-                     xt[4].part + (long)tile * Hc, row0, B, si);
+    layer_bwd_rank1<P, TH>(lds, a.DP1, a.TW, Hc, a.act, y2, Hc, a.DP0, xt[4].part + (long)tile * Hc, row0, B, si);
     save_xt<P>(lds, a.DP0, 0, Hc, xt[4].dp, a.ld, TR, row0);
     const GDesc nx2 = bwd_of(cr[2], 0);
     layer_bwd<P, TH>(lds, R, a.DP0, cr[4], 0, Hc, &nx2, a.act, y1, Hc, NO32, nullptr, 0, a.DP1,
@@ -208,8 +259,7 @@ __global__ __launch_bounds__(NTH) void critic_kernel(CriticArgs a) {
     save_xt<P>(lds, a.DP1, 0, Hc, xt[2].dp, a.ld, TR, row0);
     layer_bwd<P, TH>(lds, R, a.DP1, cr[2], 0, Hc, nullptr, ACT_NONE, nullptr, 0, a.DY, nullptr, 0, NO16, nullptr,
                      row0, B, si);
-    norm_bwd<P>(lds, a.DY, a.H0, mean, Hc, 1e-8f, dot, a.DP0, xt[0].dp, a.ld, xt[0].part + (long)tile * Hc,
-                row0, B);
+    norm_bwd<P>(lds, a.DY, a.H0, mean, Hc, 1e-8f, a.DP0, xt[0].dp, a.ld, xt[0].part + (long)tile * Hc, row0, B);
 }
 
 // ---------------------------------------------------------------- encoder
@@ -247,7 +297,7 @@ __global__ __launch_bounds__(NTH) void encoder_kernel(EncoderArgs a) {
     const int row0 = blockIdx.x * TR, B = a.B, Z = a.Z, He = a.He, tile = blockIdx.x;
     const long ld = a.ld;
     const bool split = gridDim.y == 2, producer = split && blockIdx.y == 0;
-    float *mean = (float *)(lds + a.small_off), *dot = mean + TR;
+    float *mean = (float *)(lds + a.small_off);
     int si = 0;
     FSTAMP(si);
     RowStage sns, sa, ss;
@@ -341,7 +391,7 @@ __global__ __launch_bounds__(NTH) void encoder_kernel(EncoderArgs a) {
     // d zs from the zs columns of zsa1's input, then AvgL1Norm backward
     layer_bwd<P, TH>(lds, R, a.DP0, a.e[3], 0, Z, &nx5, ACT_NONE, nullptr, 0, a.NZ, nullptr, 0, NO16, nullptr, row0, B,
                      si);
-    norm_bwd<P>(lds, a.NZ, a.H3, mean, Z, 1e-8f, dot, a.DP1, a.xt[2].dp, ld, a.xt[2].part + (long)tile * Z, row0, B);
+    norm_bwd<P>(lds, a.NZ, a.H3, mean, Z, 1e-8f, a.DP1, a.xt[2].dp, ld, a.xt[2].part + (long)tile * Z, row0, B);
     __syncthreads();
     const GDesc nx6 = bwd_of(a.e[1], 0);
     layer_bwd<P, TH>(lds, R, a.DP1, a.e[2], 0, He, &nx6, a.act, a.y1, He, NO32, nullptr, 0, a.DP0,
@@ -427,7 +477,7 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int row0 = blockIdx.x * TR, B = a.B, Z = a.Z, h = blockIdx.y, Hc = a.Hc;
     const Lin *cr = a.cr + h;
-    float *mean = (float *)(lds + a.small_off), *dot = mean + TR;
+    float *mean = (float *)(lds + a.small_off);
     float *y1 = a.yc[0] + (long)h * B * Hc, *y2 = a.yc[1] + (long)h * B * Hc;
     int si = 0;
     FSTAMP(si);
@@ -438,8 +488,8 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     row_issue(sz, a.zsa_out, Z, Z, row0, B);
     row_issue(szs, a.zs, Z, Z, row0, B);
     thin_issue(tw, cr[0].w, cr[0].ldw, a.S, true, a.A, Hc);
-    ThinStage<1> tq;
-    if constexpr (BC) thin_issue(tq, cr[6].w, cr[6].ldw, 0, false, 1, Hc);
+    ThinStage<1> tq;  // q3's weights: its rank-1 dX (and, BC, Q itself)
+    thin_issue(tq, cr[6].w, cr[6].ldw, 0, false, 1, Hc);
     Ring<TH> R;
     ring_fill<TH>(R, fwd_of(cr[0]));
     zero_lds(lds, a.lds);
@@ -450,7 +500,7 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     row_put16<P>(lds, szs, a.CAT, Hc + Z, Z, row0, B);
     if constexpr (P != PREC_F32) {
         thin_put<P>(lds, tw, a.TW, a.A, Hc);
-        if constexpr (BC) thin_put<P>(lds, tq, a.TW2, 1, Hc);
+        thin_put<P>(lds, tq, a.TW2, 1, Hc);
     }
     __syncthreads();
     // Q = critic(state, actor, zsa, zs) with the updated critic (:270)
@@ -461,10 +511,10 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     // (fp32: the thin weights' region lies in CAT, dead from here on)
     if constexpr (P == PREC_F32) {
         thin_put<P>(lds, tw, a.TW, a.A, Hc);
-        if constexpr (BC) thin_put<P>(lds, tq, a.TW2, 1, Hc);
+        thin_put<P>(lds, tq, a.TW2, 1, Hc);
     }
-    const GDesc b3 = bwd_of(cr[6], 0);
-    layer_fwd<P, 1, TH>(lds, R, a.H1, cr[4], &b3, a.act_critic, a.H2, 0, NO32, y2, Hc, row0, B, si);
+    const GDesc nx7 = bwd_of(cr[4], 0);  // (q3's dX is a rank-1 product on the VALU)
+    layer_fwd<P, 1, TH>(lds, R, a.H1, cr[4], &nx7, a.act_critic, a.H2, 0, NO32, y2, Hc, row0, B, si);
     if constexpr (BC) {
         // Q = q3(H2) of this head, then sum |Q| over the tile's live rows in
         // row order (:273, the |Q| mean's partial): one lane, one store
@@ -482,9 +532,7 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     __syncthreads();
     make_dp<P>(lds, a.F, 1, ACT_NONE, nullptr, 0, a.DP1, nullptr, row0, B);
     __syncthreads();
-    const GDesc nx7 = bwd_of(cr[4], 0);
-    layer_bwd<P, TH>(lds, R, a.DP1, cr[6], 0, Hc, &nx7, a.act_critic, y2, Hc, NO32, nullptr, 0, a.DP0, nullptr, row0,
-                     B, si);
+    layer_bwd_rank1<P, TH>(lds, a.DP1, a.TW2, Hc, a.act_critic, y2, Hc, a.DP0, nullptr, row0, B, si);
     const GDesc nx8 = bwd_of(cr[2], Hc);
     layer_bwd<P, TH>(lds, R, a.DP0, cr[4], 0, Hc, &nx8, a.act_critic, y1, Hc, NO32, nullptr, 0, a.DP1, nullptr, row0,
                      B, si);
@@ -496,7 +544,7 @@ __global__ __launch_bounds__(NTH) void actor_b_kernel(ActorArgs a) {
     layer_bwd<P, TH>(lds, R, a.DP1, cr[2], 0, Hc, nullptr, ACT_NONE, nullptr, 0, a.DY, nullptr, 0, NO16, nullptr,
                      row0, B, si);
     FSTAMP(si);
-    norm_bwd<P>(lds, a.DY, a.H0, mean, Hc, 1e-8f, dot, a.DP0, nullptr, 0, nullptr, row0, B);
+    norm_bwd<P>(lds, a.DY, a.H0, mean, Hc, 1e-8f, a.DP0, nullptr, 0, nullptr, row0, B);
     __syncthreads();
     FSTAMP(si);
     thin<P, THIN_NC>(lds, a.DP0, 0, Hc, a.TW, a.A, a.F, 1.f / Ty<P>::gs);
@@ -516,7 +564,7 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int row0 = blockIdx.x * TR, B = a.B, Z = a.Z, Ha = a.Ha, He = a.He, A = a.A, tile = blockIdx.x;
     const long ld = a.ld;
-    float *mean = (float *)(lds + a.small_off), *dot = mean + TR;
+    float *mean = (float *)(lds + a.small_off);
     int si = 0;
     FSTAMP(si);
     // d zsa = sum over the heads -> the fixed encoder's zsa3 dP (no activation)
@@ -527,6 +575,13 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     row_issue(sh, a.h0, Ha, Ha, row0, B);
     const float m0 = ldg(a.mean0 + min(row0 + (int)(threadIdx.x % TR), B - 1));
     thin_issue(tw, a.fe[3].w, a.fe[3].ldw, Z, true, A, He);
+    // the tanh' block's operands of element threadIdx.x (< 16 A <= NTH) with the
+    // kernel-start batch: the action and both critic heads' d action.  (Issued
+    // behind the ring's loads instead, the TH 4 BC kernels take 171 VGPRs, past
+    // the 168 of three waves per SIMD.)
+    const int ek = min((int)threadIdx.x, TR * A - 1), eb = min(row0 + ek / A, B - 1), ec = ek % A;
+    const float e_y = ldg(a.act_out + (long)eb * A + ec), e_d0 = ldg(a.da + (long)eb * A + ec),
+                e_d1 = ldg(a.da + ((long)B + eb) * A + ec);
     RowStage sb;
     const int nq = 2 * (int)gridDim.x;
     float q0 = 0.f;
@@ -568,12 +623,12 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
             cbc = a.bc_scale * (sum * a.inv_2b);
         }
     }
-    for (int k = threadIdx.x; k < TR * A; k += NTH) {
-        const int r = k / A, c = k - r * A, b = row0 + r;
+    if ((int)threadIdx.x < TR * A) {
+        const int k = threadIdx.x, r = k / A, c = k - r * A, b = row0 + r;
         float v = 0.f;
         if (b < B) {
-            const float y = ldg(a.act_out + (long)b * A + c);
-            float d = *p32(lds, a.F, r, c) + ldg(a.da + (long)b * A + c) + ldg(a.da + ((long)B + b) * A + c);
+            const float y = e_y;
+            float d = *p32(lds, a.F, r, c) + e_d0 + e_d1;
             if constexpr (BC) d += cbc * (y - *p32(lds, a.AB, r, c));
             v = d * (1.f - y * y);
         }
@@ -594,8 +649,7 @@ __global__ __launch_bounds__(NTH) void actor_c_kernel(ActorArgs a) {
     layer_bwd<P, TH>(lds, R, a.DP1, a.ac[1], 0, Ha, nullptr, ACT_NONE, nullptr, 0, a.DY, nullptr, 0, NO16, nullptr,
                      row0, B, si);
     FSTAMP(si);
-    norm_bwd<P>(lds, a.DY, a.H0, mean, Ha, 1e-8f, dot, a.DP0, a.xt[0].dp, ld, a.xt[0].part + (long)tile * Ha, row0,
-                B);
+    norm_bwd<P>(lds, a.DY, a.H0, mean, Ha, 1e-8f, a.DP0, a.xt[0].dp, ld, a.xt[0].part + (long)tile * Ha, row0, B);
     __syncthreads();
     FSTAMP(si);
 }
@@ -1040,7 +1094,7 @@ int td7f_critic_phase(int32_t phase, int32_t prec, const int32_t *act, const td7
     if (prec != PREC_F32) g.DY = b.r32(TR, g.Hc);
     g.F = b.r32(TR, 16);
     g.TW = b.r32(1, g.Hc);
-    const R32 sm = b.r32(1, 2 * TR);
+    const R32 sm = b.r32(1, TR);
     g.small_off = sm.off;
     g.lds_bytes = b.off;
     return DISPATCH(prec, th, critic_kernel, dim3((B + TR - 1) / TR, 2), b.off, g, (hipStream_t)stream);
@@ -1093,7 +1147,7 @@ int td7f_encoder(int32_t prec, const int32_t *act, const td7f_lin *enc, const fl
     g.H3 = b.r32(TR, g.Z);
     g.NZ = b.r32(TR, w);
     g.DY = b.r32(TR, w);
-    const R32 sm = b.r32(1, 2 * TR);
+    const R32 sm = b.r32(1, TR);
     g.small_off = sm.off;
     g.lds_bytes = b.off;
     g.nz = nz_ws;
@@ -1174,11 +1228,11 @@ static int actor_pass(bool bc, int32_t prec, int32_t phase, const int32_t *act, 
             // fp32 (as td7f_critic): dP images and the thin weights (staged
             // after q1's forward) in CAT, dY over H1 | H2
             if (!alias_pair(g.CAT, ld16(g.Hc, kd), g.DP0, g.DP1) || !alias32(g.H1, g.H2, g.Hc, g.DY)) return EXO_EINVAL;
-            // (BC: q3's row behind them)
+            // (q3's row behind them)
             const int tw = g.DP1.off + round_up(TR * g.DP1.ld * 2, 16);
             g.TW = R32{tw, g.Hc};
             g.TW2 = R32{tw + THIN_NC * g.Hc * 4, g.Hc};
-            if (tw + (THIN_NC + (bc ? 1 : 0)) * g.Hc * 4 > g.CAT.off + TR * g.CAT.ld * 2) return EXO_EINVAL;
+            if (tw + (THIN_NC + 1) * g.Hc * 4 > g.CAT.off + TR * g.CAT.ld * 2) return EXO_EINVAL;
         } else {
             g.DP0 = b.r16(TR, ld16(g.Hc));
             g.DP1 = b.r16(TR, ld16(g.Hc));
@@ -1187,7 +1241,7 @@ static int actor_pass(bool bc, int32_t prec, int32_t phase, const int32_t *act, 
         if (prec != PREC_F32) g.DY = b.r32(TR, g.Hc);
         g.F = b.r32(TR, 16);
         if (prec != PREC_F32) g.TW = b.r32(THIN_NC, g.Hc);
-        if (prec != PREC_F32 && bc) g.TW2 = b.r32(1, g.Hc);
+        if (prec != PREC_F32) g.TW2 = b.r32(1, g.Hc);
     } else {
         g.DP0 = b.r16(TR, ld16(std::max(hmax, g.Z), kd));
         g.DP1 = b.r16(TR, ld16(std::max(hmax, g.Z), kd));
@@ -1200,7 +1254,7 @@ static int actor_pass(bool bc, int32_t prec, int32_t phase, const int32_t *act, 
             g.QS = b.r32(1, 2 * tiles);
         }
     }
-    const R32 sm = b.r32(1, 2 * TR);
+    const R32 sm = b.r32(1, TR);
     g.small_off = sm.off;
     g.lds = b.off;
     const hipStream_t st = (hipStream_t)stream;
