@@ -323,16 +323,22 @@ __global__ void lap_sample_kernel(const float *tree, int cap, int levels, const 
     idx[(size_t)s * batch + b] = i;
 }
 
-// LAP.update_priority (:113-117)
-__global__ __launch_bounds__(UPD_THREADS) void lap_update_kernel(float *tree, float *maxp, int cap, int levels,
-                                                                 const int32_t *idx, const float *prio,
-                                                                 int batch) {
-    const int s = blockIdx.x;
-    float *T = stratum_tree(tree, s, cap);
-    const int32_t *I = idx + (size_t)s * batch;
-    const float *P = prio + (size_t)s * batch;
-    __shared__ float red[UPD_THREADS / 64];
-    __shared__ int32_t li[UPD_THREADS];
+// TdPrio (lap_update_sample_td): the priorities computed in the update from the
+// critic pass's |td| of both heads, prio = max(|td0|, |td1|, min_priority)^alpha
+// (TD7_multi_agent.py:259, the expression td7f_wgrad evaluates), so the update
+// need not wait for the weight-gradient launch; written to `out` if non-null.
+struct TdPrio {
+    const float *td;  // [B][2]; nullptr: the priorities are given (prio)
+    float alpha, minp;
+    float *out;
+};
+
+// LAP.update_priority's leaf pass for stratum s (:113-117): the batch's indices
+// I staged in LDS (li, UPD_THREADS of them at a time), a leaf written by the
+// last of its duplicates, priorities P or tp's.  Returns the thread's running
+// maximum of the batch's priorities.
+__device__ __forceinline__ float update_leaves(float *T, int cap, const int32_t *I, int batch, const TdPrio &tp,
+                                               const float *P, int s, int32_t *li) {
     float mx = 0.0f;
     for (int b0 = 0; b0 < batch; b0 += UPD_THREADS) { // the batch's indices staged in LDS
         const int nb = min(UPD_THREADS, batch - b0);
@@ -345,18 +351,50 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_kernel(float *tree, fl
             bool last = true; // a later duplicate overwrites this one
             for (int k = threadIdx.x + 1; k < nb; ++k) last &= (li[k] != me);
             for (int b2 = b0 + nb; b2 < batch; ++b2) last &= (I[b2] != me);
-            if (last) T[cap + me] = P[b];
-            mx = fmaxf(mx, P[b]);
+            float pb;
+            if (tp.td) {
+                const long d = (long)s * batch + b;
+                pb = powf(fmaxf(fmaxf(tp.td[2 * d], tp.td[2 * d + 1]), tp.minp), tp.alpha);
+                if (tp.out) tp.out[d] = pb;
+            } else {
+                pb = P[b];
+            }
+            if (last) T[cap + me] = pb;
+            mx = fmaxf(mx, pb);
         }
     }
+    return mx;
+}
+
+// The workgroup's maximum into *maxp, in two steps with a barrier of the
+// caller's between them (propagate*'s, where there is one): every wave's
+// maximum to red[], then thread 0's atomic.
+__device__ __forceinline__ float wave_max_to(float *red, float mx) {
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    propagate(T, cap, levels, I, batch);
+    return mx;
+}
+__device__ __forceinline__ void block_max_to(float *maxp, float mx, const float *red) {
     if (threadIdx.x == 0) {
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, red[w]);
-        // priorities are >= min_priority^alpha > 0: int order == float order
+        // priorities are >= min_priority^alpha > 0 (leaves >= 0): int order == float order
         atomicMax(reinterpret_cast<int *>(maxp), __float_as_int(mx));
     }
+}
+
+// LAP.update_priority (:113-117)
+__global__ __launch_bounds__(UPD_THREADS) void lap_update_kernel(float *tree, float *maxp, int cap, int levels,
+                                                                 const int32_t *idx, const float *prio,
+                                                                 int batch) {
+    const int s = blockIdx.x;
+    float *T = stratum_tree(tree, s, cap);
+    const int32_t *I = idx + (size_t)s * batch;
+    __shared__ float red[UPD_THREADS / 64];
+    __shared__ int32_t li[UPD_THREADS];
+    float mx = update_leaves(T, cap, I, batch, TdPrio{nullptr, 0.f, 0.f, nullptr}, prio + (size_t)s * batch, s, li);
+    mx = wave_max_to(red, mx);
+    propagate(T, cap, levels, I, batch);
+    block_max_to(maxp, mx, red);
 }
 
 // LAP.reset_max_priority (:119-120): max over every leaf of every stratum.
@@ -369,13 +407,9 @@ __global__ void lap_reset_max_kernel(const float *tree, float *maxp, int cap, in
         const size_t s = k / cap, i = k % cap;
         mx = fmaxf(mx, tree[s * 2 * cap + cap + i]);
     }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    mx = wave_max_to(red, mx);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, red[w]);
-        atomicMax(reinterpret_cast<int *>(maxp), __float_as_int(mx));
-    }
+    block_max_to(maxp, mx, red);
 }
 
 __global__ void lap_totals_kernel(const float *tree, int cap, int n_strata, float *out) {
@@ -398,12 +432,42 @@ __global__ void lap_init_kernel(float *maxp) { *maxp = 1.0f; } // max_priority =
 // Phase 2 (many workgroups): one wavefront per row copies its transition.
 constexpr int STORE_CHUNK = UPD_THREADS * 4;
 
+// The calling thread's exclusive prefix of v over the UPD_THREADS-thread
+// workgroup (wave __shfl_up ladder, the waves' sums in wsum[UPD_THREADS / 64],
+// thread 0's serial pass over them), and the workgroup's total through `total`
+// (from *total_lds, into a register before returning).  Two barriers; a caller
+// that scans again keeps a barrier of its own before the next call, which
+// overwrites wsum and *total_lds.
+__device__ __forceinline__ int block_scan_excl(int v, int *wsum, int *total_lds, int &total) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    int incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    if (t == 0) {
+        int acc = 0;
+        for (int k = 0; k < UPD_THREADS / 64; ++k) {
+            const int w = wsum[k];
+            wsum[k] = acc;
+            acc += w;
+        }
+        *total_lds = acc;
+    }
+    __syncthreads();
+    total = *total_lds;
+    return wsum[wv] + incl - v;
+}
+
 template <int RANK_RPT>
 __global__ __launch_bounds__(UPD_THREADS) void lap_store_rank_kernel(float *tree, const float *maxp, int cap,
                                                                      int levels, int capacity, int32_t *ring_ptr,
                                                                      int32_t *ring_size, const int32_t *strata,
                                                                      const uint8_t *active, int n, int32_t *row_of) {
-    const int s = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int s = blockIdx.x, t = threadIdx.x;
     float *T = stratum_tree(tree, s, cap);
     __shared__ int wsum[UPD_THREADS / 64];
     __shared__ int chunk_total;
@@ -430,26 +494,8 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_rank_kernel(float *tree
             f[k] = f[k] && st[k] == s;
             cnt += f[k];
         }
-        // block-wide exclusive scan of cnt
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-            for (int k = 0; k < UPD_THREADS / 64; ++k) {
-                const int v = wsum[k];
-                wsum[k] = acc;
-                acc += v;
-            }
-            chunk_total = acc;
-        }
-        __syncthreads();
-        int rank = offset + wsum[wv] + incl - cnt;
+        int total;
+        int rank = offset + block_scan_excl(cnt, wsum, &chunk_total, total);
 #pragma unroll
         for (int k = 0; k < RANK_RPT; ++k) {
             const int i = base + RANK_RPT * t + k;
@@ -465,7 +511,6 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_rank_kernel(float *tree
                 row_of[i] = row0 + capacity; // inactive env: the trash row
             }
         }
-        const int total = chunk_total;
         __syncthreads();
         offset += total;
     }
@@ -492,13 +537,32 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_rank_kernel(float *tree
 // shared size, :76).
 __device__ __forceinline__ long long mult_below(long long x, int E) { return (x + E - 1) / E; }
 
+// The shared pointer's slot for an add whose count c has mr = mult_below(c, E),
+// from the pointer ptr0 at count0 (m0 = mult_below(count0, E)).
+__device__ __forceinline__ int ref_slot(long long ptr0, long long m0, long long mr, int capacity) {
+    long long v = ptr0 + (mr - m0); // ptr0 < capacity, mr - m0 <= n / E + 1
+    if (v >= capacity) v -= capacity;
+    if (v >= capacity) v %= capacity;
+    return (int)v;
+}
+
+// {ptr, count, size} after n_act more adds
+struct RefState {
+    long long ptr, count, size;
+};
+__device__ __forceinline__ RefState ref_advance(long long ptr0, long long count0, long long size0, long long n_act,
+                                                int E, int capacity) {
+    const long long adv = mult_below(count0 + n_act, E) - mult_below(count0, E);
+    return {(ptr0 + adv) % capacity, count0 + n_act, min(size0 + adv, (long long)capacity)};
+}
+
 __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_slots_kernel(int capacity, int E, long long *ref,
                                                                           int32_t *ring_size,
                                                                           const int32_t *strata,
                                                                           const uint8_t *active, int n,
                                                                           int32_t *rank_row, int32_t *slot_of,
                                                                           int32_t *row_of) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x;
     __shared__ int wsum[UPD_THREADS / 64];
     __shared__ int chunk_total;
     const long long ptr0 = ref[0], count0 = ref[1], size0 = ref[2];
@@ -512,25 +576,8 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_slots_kernel(int ca
             f[k] = (i < n && strata[i] >= 0 && strata[i] < E && (!active || active[i])) ? 1 : 0;
             cnt += f[k];
         }
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-            for (int k = 0; k < UPD_THREADS / 64; ++k) {
-                const int v = wsum[k];
-                wsum[k] = acc;
-                acc += v;
-            }
-            chunk_total = acc;
-        }
-        __syncthreads();
-        int rank = offset + wsum[wv] + incl - cnt;
+        int total;
+        int rank = offset + block_scan_excl(cnt, wsum, &chunk_total, total);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int i = base + 4 * t + k;
@@ -544,7 +591,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_slots_kernel(int ca
                 slot_of[i] = -1;
             }
         }
-        offset += chunk_total;
+        offset += total;
         __syncthreads();
     }
     __threadfence_block();
@@ -562,21 +609,17 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_slots_kernel(int ca
         const long long qend = mr * E - count0;
         const int qmax = (int)min((long long)min(r + E, n_act) - 1, qend);
         for (int q = r + 1; q <= qmax; ++q) win &= rank_row[q] != s;
-        long long v = ptr0 + (mr - m0); // ptr0 < capacity, mr - m0 <= n / E + 1
-        if (v >= capacity) v -= capacity;
-        if (v >= capacity) v %= capacity;
-        const int slot = (int)v;
+        const int slot = ref_slot(ptr0, m0, mr, capacity);
         slot_of[i] = win ? slot : -1;
         row_of[i] = win ? s * (capacity + 1) + slot : -1;
     }
     __syncthreads();
-    const long long adv = mult_below(count0 + n_act, E) - m0;
-    const long long size = min(size0 + adv, (long long)capacity);
-    for (int s = t; s < E; s += blockDim.x) ring_size[s] = (int32_t)size;
+    const RefState nx = ref_advance(ptr0, count0, size0, n_act, E, capacity);
+    for (int s = t; s < E; s += blockDim.x) ring_size[s] = (int32_t)nx.size;
     if (t == 0) {
-        ref[0] = (ptr0 + adv) % capacity;
-        ref[1] = count0 + n_act;
-        ref[2] = size;
+        ref[0] = nx.ptr;
+        ref[1] = nx.count;
+        ref[2] = nx.size;
     }
 }
 
@@ -597,11 +640,29 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_slots_kernel(int ca
 __device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ void st4(float *p, float4 v) { *reinterpret_cast<float4 *>(p) = v; }
 
+// One env step's transitions as the store kernels receive them: row i of
+// state / next_state [n][state_dim], action [n][action_dim] (stored divided by
+// action_scale), reward [n], done [n] (stored as not_done = 1 - done).
+struct Rows {
+    const float *state, *action, *next_state, *reward;
+    const uint8_t *done;
+    float action_scale;
+};
+
+// The rows are whole float4s, 16-byte aligned, in the storage and in the
+// caller's state / next_state arrays a, b (the copies' float4 path).
+__host__ __device__ __forceinline__ bool rows_vec(const lap_storage_desc &st, const float *a, const float *b) {
+    return (st.state_dim & 3) == 0 &&
+           ((reinterpret_cast<uintptr_t>(st.state) | reinterpret_cast<uintptr_t>(st.next_state) |
+             reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
+// The transitions in.*[ri[j]] for j = j0, j0 + step, ... < m of stratum s to the
+// slots sl[j] (< 0: skipped), item by item over the nt threads t.
 template <bool VEC>
-__device__ __forceinline__ void copy_rows(const lap_storage_desc &st, const float *state, const float *action,
-                                          const float *next_state, const float *reward, const uint8_t *done,
-                                          float action_scale, const int32_t *ri, const int32_t *sl, int s,
-                                          int capacity, int j0, int step, int m, int t, int nt) {
+__device__ __forceinline__ void copy_rows(const lap_storage_desc &st, const Rows &in, const int32_t *ri,
+                                          const int32_t *sl, int s, int capacity, int j0, int step, int m, int t,
+                                          int nt) {
     const int sd = st.state_dim, ad = st.action_dim;
     const int sdv = VEC ? sd / 4 : sd;        // state items per row (float4 or float)
     const int per = 2 * sdv + ad + 2;         // state, next_state, action, reward, not_done
@@ -625,7 +686,7 @@ __device__ __forceinline__ void copy_rows(const lap_storage_desc &st, const floa
             if (c < 2 * sdv) {
                 const bool nx = c >= sdv;
                 const int e = nx ? c - sdv : c;
-                const float *src = (nx ? next_state : state) + i * sd;
+                const float *src = (nx ? in.next_state : in.state) + i * sd;
                 if (VEC) {
                     v[u] = ld4(src + 4 * e);
                     dst[u] = r * sd + 4 * e;
@@ -636,15 +697,15 @@ __device__ __forceinline__ void copy_rows(const lap_storage_desc &st, const floa
                 kind[u] = nx ? 1 : 0;
             } else if (c < 2 * sdv + ad) {
                 const int e = c - 2 * sdv;
-                v[u].x = action[i * ad + e] / action_scale;
+                v[u].x = in.action[i * ad + e] / in.action_scale;
                 dst[u] = r * ad + e;
                 kind[u] = 2;
             } else if (c == 2 * sdv + ad) {
-                v[u].x = reward[i];
+                v[u].x = in.reward[i];
                 dst[u] = r;
                 kind[u] = 3;
             } else {
-                v[u].x = 1.0f - (done[i] ? 1.0f : 0.0f);
+                v[u].x = 1.0f - (in.done[i] ? 1.0f : 0.0f);
                 dst[u] = r;
                 kind[u] = 4;
             }
@@ -667,151 +728,6 @@ __device__ __forceinline__ void copy_rows(const lap_storage_desc &st, const floa
     }
 }
 
-// The vectorised insert as ONE launch (r05, opt-in: EXO_LAP_STORE_FUSED=1,
-// measured slower in the loop; lap_store_batch at n <= 8,192):
-// lap_store_rank_kernel's scan, leaves and span propagation, and the copy of
-// the stratum's rows by the same workgroup -- the scan leaves each rank's env
-// and slot in LDS, the workgroup's 1,024 threads copy the rows (8 items in
-// flight per thread, float4 state rows where aligned).  One workgroup per
-// stratum reads and writes its own ring pointer, so no other workgroup needs
-// it.  The same rows, slots, leaves and sums as the two launches (an inactive
-// row's copy to the trash row is skipped: nothing reads that row).
-constexpr int STORE_FUSED_MAX = 8192;
-
-template <bool VEC>
-__global__ __launch_bounds__(UPD_THREADS) void lap_store_fused_kernel(
-    float *tree, const float *maxp, int cap, int levels, int capacity, int32_t *ring_ptr, int32_t *ring_size,
-    const int32_t *strata, const uint8_t *active, int n, int32_t *row_of, lap_storage_desc st, const float *state,
-    const float *action, const float *next_state, const float *reward, const uint8_t *done, float action_scale) {
-    constexpr int RPT = 4;
-    const int s = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    float *T = stratum_tree(tree, s, cap);
-    __shared__ int wsum[UPD_THREADS / 64];
-    __shared__ int chunk_total;
-    __shared__ int32_t ri[STORE_FUSED_MAX];
-    const float p = *maxp;
-    const int ptr0 = ring_ptr[s];
-    const int row0 = s * (capacity + 1);
-    int offset = 0;
-    for (int base = 0; base < n; base += RPT * UPD_THREADS) {
-        int stk[RPT], cnt = 0;
-        bool f[RPT];
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const int i = base + RPT * t + k;
-            stk[k] = i < n ? strata[i] : -1;
-            f[k] = i < n && (!active || active[i]) && stk[k] == s;
-            cnt += f[k];
-        }
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-            for (int k = 0; k < UPD_THREADS / 64; ++k) {
-                const int v = wsum[k];
-                wsum[k] = acc;
-                acc += v;
-            }
-            chunk_total = acc;
-        }
-        __syncthreads();
-        int rank = offset + wsum[wv] + incl - cnt;
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const int i = base + RPT * t + k;
-            if (i >= n) continue;
-            if (s == 0 && (stk[k] < 0 || stk[k] >= (int)gridDim.x)) row_of[i] = -1;
-            if (stk[k] != s) continue;
-            if (f[k]) {
-                const int slot = (ptr0 + rank) % capacity;
-                row_of[i] = row0 + slot;
-                T[cap + slot] = p;
-                ri[rank] = i;
-                ++rank;
-            } else {
-                row_of[i] = row0 + capacity;
-            }
-        }
-        const int total = chunk_total;
-        __syncthreads();
-        offset += total;
-    }
-    // the stratum's rows: rank q -> slot (ptr0 + q) % capacity
-    {
-        const int sd = st.state_dim, ad = st.action_dim;
-        const int sdv = VEC ? sd / 4 : sd;
-        const int per = 2 * sdv + ad + 2;
-        const int items = offset * per;
-        constexpr int U = 8;
-        for (int it0 = t; it0 < items; it0 += U * UPD_THREADS) {
-            float4 v[U];
-            long dst[U];
-            int kind[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int it = it0 + u * UPD_THREADS;
-                kind[u] = -1;
-                if (it >= items) continue;
-                const int q = it / per, c = it - q * per;
-                const long r = (long)row0 + (ptr0 + q) % capacity;
-                const long i = ri[q];
-                if (c < 2 * sdv) {
-                    const bool nx = c >= sdv;
-                    const int e = nx ? c - sdv : c;
-                    const float *src = (nx ? next_state : state) + i * sd;
-                    if (VEC) {
-                        v[u] = ld4(src + 4 * e);
-                        dst[u] = r * sd + 4 * e;
-                    } else {
-                        v[u].x = src[e];
-                        dst[u] = r * sd + e;
-                    }
-                    kind[u] = nx ? 1 : 0;
-                } else if (c < 2 * sdv + ad) {
-                    const int e = c - 2 * sdv;
-                    v[u].x = action[i * ad + e] / action_scale;
-                    dst[u] = r * ad + e;
-                    kind[u] = 2;
-                } else if (c == 2 * sdv + ad) {
-                    v[u].x = reward[i];
-                    dst[u] = r;
-                    kind[u] = 3;
-                } else {
-                    v[u].x = 1.0f - (done[i] ? 1.0f : 0.0f);
-                    dst[u] = r;
-                    kind[u] = 4;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                switch (kind[u]) {
-                case 0:
-                    if (VEC) st4(st.state + dst[u], v[u]); else st.state[dst[u]] = v[u].x;
-                    break;
-                case 1:
-                    if (VEC) st4(st.next_state + dst[u], v[u]); else st.next_state[dst[u]] = v[u].x;
-                    break;
-                case 2: st.action[dst[u]] = v[u].x; break;
-                case 3: st.reward[dst[u]] = v[u].x; break;
-                case 4: st.not_done[dst[u]] = v[u].x; break;
-                default: break;
-                }
-            }
-        }
-    }
-    propagate_span(T, cap, levels, capacity, ptr0, offset);
-    if (t == 0) {
-        ring_ptr[s] = (ptr0 + offset) % capacity;
-        ring_size[s] = min(ring_size[s] + offset, capacity);
-    }
-}
-
 // The training loop's per-step mask advance, optionally done by the insert's
 // last workgroup out (lap_store_batch_ref_fused_adv): every workgroup has read
 // the step's mask by then.  exo_active_advance_score's arithmetic: score +=
@@ -829,13 +745,12 @@ struct MaskAdvance {
 template <bool VEC>
 __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
     float *tree, const float *maxp, int cap, int levels, int capacity, int E, long long *ref, int32_t *ring_size,
-    lap_storage_desc st, const float *state, const float *action, const float *next_state, const float *reward,
-    const uint8_t *done, float action_scale, const int32_t *strata, const uint8_t *active, int n,
-    uint32_t *ticket, MaskAdvance adv) {
+    lap_storage_desc st, Rows in, const int32_t *strata, const uint8_t *active, int n, uint32_t *ticket,
+    MaskAdvance adv) {
     const int s = blockIdx.x, part = blockIdx.y, K = gridDim.y;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     __shared__ int wsum[UPD_THREADS / 64];
-    __shared__ int chunk_tot, chunk_m;
+    __shared__ int chunk_total;  // (active rows) | (rows of stratum s) << 16
     __shared__ int32_t rk[STORE_CHUNK], ri[STORE_CHUNK], sl[STORE_CHUNK];
     __shared__ int carry_r, carry_i, carry_J, carry_slot;  // the chunk's last row of stratum s, decided later
     float *T = stratum_tree(tree, s, cap);
@@ -845,12 +760,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
     const long long ptr0 = ref[0], count0 = ref[1], size0 = ref[2];
     const long long m0 = mult_below(count0, E);
     const float p = *maxp;
-    auto slot_of = [&](long long r) -> int {
-        long long v = ptr0 + (mult_below(count0 + r, E) - m0);
-        if (v >= capacity) v -= capacity;
-        if (v >= capacity) v %= capacity;
-        return (int)v;
-    };
+    auto slot_of = [&](long long r) { return ref_slot(ptr0, m0, mult_below(count0 + r, E), capacity); };
     if (t == 0) carry_r = -1;
     int offset = 0, soff = 0;  // active rows / stratum-s rows before this chunk
     for (int base = 0; base < n; base += STORE_CHUNK) {
@@ -866,26 +776,8 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
             gcnt += g[k];
         }
         // block-wide exclusive scan of (cnt, gcnt) packed in one int (each <= STORE_CHUNK < 2^16)
-        int incl = cnt | (gcnt << 16);
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-            for (int k = 0; k < UPD_THREADS / 64; ++k) {
-                const int v = wsum[k];
-                wsum[k] = acc;
-                acc += v;
-            }
-            chunk_tot = acc & 0xFFFF;
-            chunk_m = acc >> 16;
-        }
-        __syncthreads();
-        const int ex = wsum[wv] + incl - (cnt | (gcnt << 16));
+        int total;
+        const int ex = block_scan_excl(cnt | (gcnt << 16), wsum, &chunk_total, total);
         int rank = offset + (ex & 0xFFFF), j = ex >> 16;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -897,7 +789,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
             rank += f[k];
         }
         __syncthreads();
-        const int m = chunk_m;
+        const int m = total >> 16;
         // the previous chunk's last row of stratum s: its successor is rk[0]
         if (t == 0) {
             carry_slot = -1;
@@ -912,8 +804,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
         }
         __syncthreads();
         if (carry_slot >= 0 && wv == 0 && carry_J % KC == cpart)
-            copy_rows<VEC>(st, state, action, next_state, reward, done, action_scale, &carry_i, &carry_slot, s,
-                           capacity, 0, 1, 1, lane, 64);
+            copy_rows<VEC>(st, in, &carry_i, &carry_slot, s, capacity, 0, 1, 1, lane, 64);
         __syncthreads();  // the loop below sets the next carry: wave 0 must be done reading this one
         for (int jj = t; jj < m; jj += UPD_THREADS) {
             const int r = rk[jj];
@@ -934,10 +825,9 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
         // this part's share of the chunk's winners: stratum-row index = cpart (mod KC)
         if (cpart >= 0) {
             const int j0 = ((cpart - soff) % KC + KC) % KC;
-            copy_rows<VEC>(st, state, action, next_state, reward, done, action_scale, ri, sl, s, capacity, j0, KC, m,
-                           t, UPD_THREADS);
+            copy_rows<VEC>(st, in, ri, sl, s, capacity, j0, KC, m, t, UPD_THREADS);
         }
-        offset += chunk_tot;
+        offset += total & 0xFFFF;
         soff += m;
         __syncthreads();
     }
@@ -951,8 +841,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
     }
     __syncthreads();
     if (carry_slot >= 0 && wv == 0 && carry_J % KC == cpart)
-        copy_rows<VEC>(st, state, action, next_state, reward, done, action_scale, &carry_i, &carry_slot, s, capacity,
-                       0, 1, 1, lane, 64);
+        copy_rows<VEC>(st, in, &carry_i, &carry_slot, s, capacity, 0, 1, 1, lane, 64);
     const int n_act = offset;
     if (part == 0 && n_act > 0) {
         __shared__ float span_buf[2 * SPAN_LDS], span_edge[2 * SPAN_LEVELS];
@@ -967,12 +856,11 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
     if (t == 0) {  // ref and the mask were read (and used) before this add: no fence needed
         last = atomicAdd(ticket, 1u) == (uint32_t)(E * K - 1);  // every workgroup has read them
         if (last) {
-            const long long na = mult_below(count0 + n_act, E) - m0;
-            const long long size = min(size0 + na, (long long)capacity);
-            for (int q = 0; q < E; ++q) ring_size[q] = (int32_t)size;
-            ref[0] = (ptr0 + na) % capacity;
-            ref[1] = count0 + n_act;
-            ref[2] = size;
+            const RefState nx = ref_advance(ptr0, count0, size0, n_act, E, capacity);
+            for (int q = 0; q < E; ++q) ring_size[q] = (int32_t)nx.size;
+            ref[0] = nx.ptr;
+            ref[1] = nx.count;
+            ref[2] = nx.size;
             *ticket = 0u;
         }
     }
@@ -983,7 +871,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
     int c = 0;
     for (int e = t; e < n; e += UPD_THREADS) {
         const uint8_t v = adv.table[(size_t)kk * n + e];
-        if (adv.score) adv.score[e] += adv.active[e] ? (double)reward[e] : 0.0;
+        if (adv.score) adv.score[e] += adv.active[e] ? (double)in.reward[e] : 0.0;
         adv.active[e] = v;
         c += v != 0;
     }
@@ -1001,32 +889,39 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_store_ref_fused_kernel(
     }
 }
 
-__global__ __launch_bounds__(256) void lap_store_copy_kernel(lap_storage_desc st, const float *state,
-                                                             const float *action, const float *next_state,
-                                                             const float *reward, const uint8_t *done,
-                                                             float action_scale, int n, const int32_t *row_of) {
+// One wavefront copies transition i of `in` to storage row r.
+__device__ __forceinline__ void store_row_wave(const lap_storage_desc &st, const Rows &in, long r, long i, int lane) {
+    const int sd = st.state_dim, ad = st.action_dim;
+    for (int k = lane; k < sd; k += 64) {
+        st.state[r * sd + k] = in.state[i * sd + k];
+        st.next_state[r * sd + k] = in.next_state[i * sd + k];
+    }
+    for (int k = lane; k < ad; k += 64) st.action[r * ad + k] = in.action[i * ad + k] / in.action_scale;
+    if (lane == 0) {
+        st.reward[r] = in.reward[i];
+        st.not_done[r] = 1.0f - (in.done[i] ? 1.0f : 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(256) void lap_store_copy_kernel(lap_storage_desc st, Rows in, int n,
+                                                             const int32_t *row_of) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= n) return;
     const long r = row_of[i];
     if (r < 0) return;
-    const int sd = st.state_dim, ad = st.action_dim;
-    for (int k = lane; k < sd; k += 64) {
-        st.state[r * sd + k] = state[(long)i * sd + k];
-        st.next_state[r * sd + k] = next_state[(long)i * sd + k];
-    }
-    for (int k = lane; k < ad; k += 64) st.action[r * ad + k] = action[(long)i * ad + k] / action_scale;
-    if (lane == 0) {
-        st.reward[r] = reward[i];
-        st.not_done[r] = 1.0f - (done[i] ? 1.0f : 0.0f);
-    }
+    store_row_wave(st, in, r, i, lane);
 }
+
+// The five arrays a sampled batch is gathered into, row d = s * batch + b.
+struct Outs {
+    float *state, *action, *next_state, *reward, *not_done;
+};
 
 // LAP.sample (:65-111) with the gather: one wavefront per draw descends the
 // tree (every lane the same path, reads broadcast) and copies the row.
 __device__ __forceinline__ void sample_descend(const float *tree, int cap, int levels, int capacity, float ud,
                                                const int32_t *size, int batch, int d, int lane, int32_t *idx,
-                                               const lap_storage_desc &st, float *o_state, float *o_action,
-                                               float *o_next, float *o_reward, float *o_not_done) {
+                                               const lap_storage_desc &st, const Outs &o) {
     const int s = d / batch;
     const float *T = tree + (size_t)s * 2 * cap;
     const int sz = size[s];
@@ -1038,13 +933,13 @@ __device__ __forceinline__ void sample_descend(const float *tree, int cap, int l
     const long r = (long)s * (capacity + 1) + i;
     const int sd = st.state_dim, ad = st.action_dim;
     for (int k = lane; k < sd; k += 64) {
-        o_state[(long)d * sd + k] = st.state[r * sd + k];
-        o_next[(long)d * sd + k] = st.next_state[r * sd + k];
+        o.state[(long)d * sd + k] = st.state[r * sd + k];
+        o.next_state[(long)d * sd + k] = st.next_state[r * sd + k];
     }
-    for (int k = lane; k < ad; k += 64) o_action[(long)d * ad + k] = st.action[r * ad + k];
+    for (int k = lane; k < ad; k += 64) o.action[(long)d * ad + k] = st.action[r * ad + k];
     if (lane == 0) {
-        o_reward[d] = st.reward[r];
-        o_not_done[d] = st.not_done[r];
+        o.reward[d] = st.reward[r];
+        o.not_done[d] = st.not_done[r];
     }
 }
 
@@ -1057,33 +952,36 @@ struct SampleRng {
     unsigned long long *counter;
     uint32_t *ticket;
 };
+// The call counter's advance, by one thread of every workgroup after the
+// workgroup's last use of `call` (= *rng.counter, read before its barrier):
+// the last workgroup out writes call + 1 and leaves the ticket zero.
+__device__ __forceinline__ void rng_ticket(const SampleRng &rng, unsigned long long call) {
+    if (atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
+        *rng.counter = call + 1ull;
+        *rng.ticket = 0u;
+    }
+}
 
 __global__ __launch_bounds__(256) void lap_sample_gather_kernel(const float *tree, int cap, int levels, int capacity,
                                                                 const float *u, const int32_t *size, int batch,
                                                                 int total, int32_t *idx, lap_storage_desc st,
-                                                                float *o_state, float *o_action, float *o_next,
-                                                                float *o_reward, float *o_not_done, SampleRng rng) {
+                                                                Outs o, SampleRng rng) {
     const int d = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (rng.counter) {
         const unsigned long long call = *rng.counter;
         __syncthreads();
         if (threadIdx.x == 0) {
             __threadfence();
-            if (atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
-                *rng.counter = call + 1ull;
-                *rng.ticket = 0u;
-            }
+            rng_ticket(rng, call);
         }
         if (d >= total) return;
         uint32_t r[4];
         philox_block(rng.seed, rng.tag, call, (uint32_t)d, r);
-        sample_descend(tree, cap, levels, capacity, u01_open_hi(r[0]), size, batch, d, lane, idx, st, o_state,
-                       o_action, o_next, o_reward, o_not_done);
+        sample_descend(tree, cap, levels, capacity, u01_open_hi(r[0]), size, batch, d, lane, idx, st, o);
         return;
     }
     if (d >= total) return;
-    sample_descend(tree, cap, levels, capacity, u[d], size, batch, d, lane, idx, st, o_state, o_action, o_next,
-                   o_reward, o_not_done);
+    sample_descend(tree, cap, levels, capacity, u[d], size, batch, d, lane, idx, st, o);
 }
 
 
@@ -1120,7 +1018,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_ref_plan_scan_kernel(const ui
                                                                         const int32_t *strata, int E,
                                                                         const long long *offs, int32_t *add_s,
                                                                         int32_t *plan) {
-    const int k = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int k = blockIdx.x, t = threadIdx.x;
     __shared__ int wsum[UPD_THREADS / 64];
     __shared__ int chunk_total;
     const uint8_t *A = table + (size_t)k * n;
@@ -1135,25 +1033,8 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_ref_plan_scan_kernel(const ui
             f[j] = (i < n && sk[j] >= 0 && sk[j] < E && A[i]) ? 1 : 0;
             cnt += f[j];
         }
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += v;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        if (t == 0) {
-            int acc = 0;
-            for (int q = 0; q < UPD_THREADS / 64; ++q) {
-                const int v = wsum[q];
-                wsum[q] = acc;
-                acc += v;
-            }
-            chunk_total = acc;
-        }
-        __syncthreads();
-        long long c = offset + wsum[wv] + incl - cnt;
+        int total;
+        long long c = offset + block_scan_excl(cnt, wsum, &chunk_total, total);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = base + 4 * t + j;
@@ -1166,7 +1047,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_ref_plan_scan_kernel(const ui
                 P[i] = -1;
             }
         }
-        offset += chunk_total;
+        offset += total;
         __syncthreads();
     }
 }
@@ -1186,10 +1067,7 @@ __global__ __launch_bounds__(256) void lap_ref_plan_slots_kernel(int32_t *plan, 
     const int s = add_s[c];
     bool win = true;
     for (long long q = c + 1; q <= qend; ++q) win &= add_s[q] != s;
-    long long v = ptr0 + (mr - m0);
-    if (v >= capacity) v -= capacity;
-    if (v >= capacity) v %= capacity;
-    plan[i] = win ? (int32_t)v : -1;
+    plan[i] = win ? ref_slot(ptr0, m0, mr, capacity) : -1;
 }
 
 // one step of the planned round: env e's transition to its slot, the episode
@@ -1199,11 +1077,8 @@ __global__ __launch_bounds__(256) void lap_ref_plan_slots_kernel(int32_t *plan, 
 // counter another one advances.
 __global__ __launch_bounds__(256) void lap_ref_step_kernel(lap_storage_desc st, const int32_t *plan, int rows, int n,
                                                            long long *kk, int par, long long *k_dev,
-                                                           const int32_t *strata, int capacity, const float *state,
-                                                           const float *action, const float *next_state,
-                                                           const float *reward, const uint8_t *done,
-                                                           float action_scale, const uint8_t *table,
-                                                           uint8_t *active, int32_t *count,
+                                                           const int32_t *strata, int capacity, Rows in,
+                                                           const uint8_t *table, uint8_t *active, int32_t *count,
                                                            const int32_t *counts_table, double *score) {
     const long long k = kk[par];
     const long long k1 = k + 1 < rows ? k + 1 : rows - 1;
@@ -1215,21 +1090,9 @@ __global__ __launch_bounds__(256) void lap_ref_step_kernel(lap_storage_desc st, 
     }
     if (e >= n) return;
     const int slot = k < rows ? plan[(size_t)k * n + e] : -1;
-    if (slot >= 0) {
-        const long r = (long)strata[e] * (capacity + 1) + slot;
-        const int sd = st.state_dim, ad = st.action_dim;
-        for (int q = lane; q < sd; q += 64) {
-            st.state[r * sd + q] = state[(long)e * sd + q];
-            st.next_state[r * sd + q] = next_state[(long)e * sd + q];
-        }
-        for (int q = lane; q < ad; q += 64) st.action[r * ad + q] = action[(long)e * ad + q] / action_scale;
-        if (lane == 0) {
-            st.reward[r] = reward[e];
-            st.not_done[r] = 1.0f - (done[e] ? 1.0f : 0.0f);
-        }
-    }
+    if (slot >= 0) store_row_wave(st, in, (long)strata[e] * (capacity + 1) + slot, e, lane);
     if (lane == 0) {
-        if (score) score[e] += active[e] ? (double)reward[e] : 0.0;
+        if (score) score[e] += active[e] ? (double)in.reward[e] : 0.0;
         active[e] = table[(size_t)k1 * n + e];
     }
 }
@@ -1261,13 +1124,11 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_ref_commit_tree_kernel(float 
 
 // the pointer and sizes after the round
 __global__ void lap_ref_commit_ref_kernel(long long *ref, long long total, int E, int capacity, int32_t *ring_size) {
-    const long long ptr0 = ref[0], count0 = ref[1], size0 = ref[2];
-    const long long adv = mult_below(count0 + total, E) - mult_below(count0, E);
-    const long long size = min(size0 + adv, (long long)capacity);
-    for (int s = 0; s < E; ++s) ring_size[s] = (int32_t)size;
-    ref[0] = (ptr0 + adv) % capacity;
-    ref[1] = count0 + total;
-    ref[2] = size;
+    const RefState nx = ref_advance(ref[0], ref[1], ref[2], total, E, capacity);
+    for (int s = 0; s < E; ++s) ring_size[s] = (int32_t)nx.size;
+    ref[0] = nx.ptr;
+    ref[1] = nx.count;
+    ref[2] = nx.size;
 }
 
 // The sampled rows gathered by their own launch (r05): lap_update_sample's
@@ -1276,53 +1137,61 @@ __global__ void lap_ref_commit_ref_kernel(long long *ref, long long total, int E
 // reward and not_done -- 64 workgroups for the bench's 8 x 128 batch instead
 // of the 8 that ran the update (9.7 of its 24.7 us, r05g).
 constexpr int GATHER_DRAWS = 16;
-__global__ __launch_bounds__(256) void lap_gather_kernel(lap_storage_desc st, int capacity, const int32_t *idx,
-                                                         int batch, int total, float *o_state, float *o_action,
-                                                         float *o_next, float *o_reward, float *o_not_done) {
+
+// The storage row of a draw and the batch row d it is gathered into.
+struct Draw {
+    long d, row;
+};
+
+// gather: (draw, item) over the nt threads t, `count` draws with draw_of(q) =
+// the q-th one's Draw; items = state, next_state (float4 where the rows are
+// 16-byte aligned), action, reward, not_done; GU items per thread loaded
+// before any is stored (the stores may alias the loads as far as the compiler
+// knows: item by item, every load would wait for the previous store -- r04
+// first cut, 54 us per launch)
+template <int GU, class DrawOf>
+__device__ __forceinline__ void gather_rows(const lap_storage_desc &st, const Outs &o, int count, int t, int nt,
+                                            DrawOf draw_of) {
     const int sd = st.state_dim, ad = st.action_dim;
-    const bool v4 = (sd & 3) == 0 && ((reinterpret_cast<uintptr_t>(st.state) | reinterpret_cast<uintptr_t>(st.next_state) |
-                                       reinterpret_cast<uintptr_t>(o_state) | reinterpret_cast<uintptr_t>(o_next)) & 15) == 0;
+    const bool v4 = rows_vec(st, o.state, o.next_state);
     const int sv = v4 ? sd / 4 : sd, per = 2 * sv + ad + 2;
-    const int d0 = blockIdx.x * GATHER_DRAWS;
-    const int nd = min(GATHER_DRAWS, total - d0);
-    const int items = nd * per;
-    constexpr int GU = 4;
-    for (int it0 = threadIdx.x; it0 < items; it0 += GU * 256) {
+    const int items = count * per;
+    for (int it0 = t; it0 < items; it0 += GU * nt) {
         float4 v[GU];
         float *dst[GU];
         bool wide[GU];
 #pragma unroll
         for (int u = 0; u < GU; ++u) {
-            const int it = it0 + u * 256;
+            const int it = it0 + u * nt;
             dst[u] = nullptr;
             wide[u] = false;
             if (it >= items) continue;
             const int q = it / per, c = it - q * per;
-            const long d = d0 + q;
-            const long row = (long)(d / batch) * (capacity + 1) + idx[d];
+            const Draw w = draw_of(q);
+            const long d = w.d, row = w.row;
             if (c < 2 * sv) {
                 const bool nx = c >= sv;
                 const int e = nx ? c - sv : c;
                 const float *src = (nx ? st.next_state : st.state) + row * sd;
-                float *o = (nx ? o_next : o_state) + d * sd;
+                float *out = (nx ? o.next_state : o.state) + d * sd;
                 if (v4) {
                     v[u] = ld4(src + 4 * e);
-                    dst[u] = o + 4 * e;
+                    dst[u] = out + 4 * e;
                     wide[u] = true;
                 } else {
                     v[u].x = src[e];
-                    dst[u] = o + e;
+                    dst[u] = out + e;
                 }
             } else if (c < 2 * sv + ad) {
                 const int e = c - 2 * sv;
                 v[u].x = st.action[row * ad + e];
-                dst[u] = o_action + d * ad + e;
+                dst[u] = o.action + d * ad + e;
             } else if (c == 2 * sv + ad) {
                 v[u].x = st.reward[row];
-                dst[u] = o_reward + d;
+                dst[u] = o.reward + d;
             } else {
                 v[u].x = st.not_done[row];
-                dst[u] = o_not_done + d;
+                dst[u] = o.not_done + d;
             }
         }
 #pragma unroll
@@ -1332,6 +1201,15 @@ __global__ __launch_bounds__(256) void lap_gather_kernel(lap_storage_desc st, in
             else *dst[u] = v[u].x;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void lap_gather_kernel(lap_storage_desc st, int capacity, const int32_t *idx,
+                                                         int batch, int total, Outs o) {
+    const int d0 = blockIdx.x * GATHER_DRAWS;
+    gather_rows<4>(st, o, min(GATHER_DRAWS, total - d0), threadIdx.x, 256, [=](int q) {
+        const long d = d0 + q;
+        return Draw{d, (long)(d / batch) * (capacity + 1) + idx[d]};
+    });
 }
 
 // LAP.update_priority (:113-117) and the NEXT LAP.sample (:65-111) as ONE
@@ -1343,127 +1221,35 @@ __global__ __launch_bounds__(256) void lap_gather_kernel(lap_storage_desc st, in
 // s * batch + b of call *counter, as lap_sample_gather_kernel) descend with
 // the nodes below TOPN read from LDS, and the workgroup gathers their rows.
 // The same sums and comparisons: bit-identical to the two launches.
-// TdPrio (lap_update_sample_td): the priorities computed here from the critic
-// pass's |td| of both heads, prio = max(|td0|, |td1|, min_priority)^alpha
-// (TD7_multi_agent.py:259, the expression td7f_wgrad evaluates), so the update
-// need not wait for the weight-gradient launch; written to `out` if non-null.
-struct TdPrio {
-    const float *td;  // [B][2]; nullptr: the priorities are given (prio)
-    float alpha, minp;
-    float *out;
-};
+// tp (lap_update_sample_td): the priorities computed here, see TdPrio.
 
 // lap_update_sample's own gather (EXO_LAP_GATHER_SPLIT=0): the rows pick[0 .. batch)
 // of stratum s, by the whole workgroup.
-__device__ __forceinline__ void gather_picked(const lap_storage_desc &st, int capacity, int s, int batch,
-                                              const int32_t *pick, float *o_state, float *o_action, float *o_next,
-                                              float *o_reward, float *o_not_done) {
-    // gather: (draw, item) over the workgroup, items = state, next_state (float4
-    // where the rows are 16-byte aligned), action, reward, not_done; GU items
-    // per thread loaded before any is stored (the stores may alias the loads as
-    // far as the compiler knows: item by item, every load would wait for the
-    // previous store -- r04 first cut, 54 us per launch)
-    const int sd = st.state_dim, ad = st.action_dim;
-    const bool v4 = (sd & 3) == 0 && ((reinterpret_cast<uintptr_t>(st.state) | reinterpret_cast<uintptr_t>(st.next_state) |
-                                       reinterpret_cast<uintptr_t>(o_state) | reinterpret_cast<uintptr_t>(o_next)) & 15) == 0;
-    const int sv = v4 ? sd / 4 : sd, per = 2 * sv + ad + 2;
-    const int items = min(batch, UPD_THREADS) * per;
-    constexpr int GU = 8;
-    for (int it0 = threadIdx.x; it0 < items; it0 += GU * UPD_THREADS) {
-        float4 v[GU];
-        float *dst[GU];
-        bool wide[GU];
-#pragma unroll
-        for (int u = 0; u < GU; ++u) {
-            const int it = it0 + u * UPD_THREADS;
-            dst[u] = nullptr;
-            wide[u] = false;
-            if (it >= items) continue;
-            const int b = it / per, c = it - b * per;
-            const long d = (long)s * batch + b;
-            const long row = (long)s * (capacity + 1) + pick[b];
-            if (c < 2 * sv) {
-                const bool nx = c >= sv;
-                const int e = nx ? c - sv : c;
-                const float *src = (nx ? st.next_state : st.state) + row * sd;
-                float *o = (nx ? o_next : o_state) + d * sd;
-                if (v4) {
-                    v[u] = ld4(src + 4 * e);
-                    dst[u] = o + 4 * e;
-                    wide[u] = true;
-                } else {
-                    v[u].x = src[e];
-                    dst[u] = o + e;
-                }
-            } else if (c < 2 * sv + ad) {
-                const int e = c - 2 * sv;
-                v[u].x = st.action[row * ad + e];
-                dst[u] = o_action + d * ad + e;
-            } else if (c == 2 * sv + ad) {
-                v[u].x = st.reward[row];
-                dst[u] = o_reward + d;
-            } else {
-                v[u].x = st.not_done[row];
-                dst[u] = o_not_done + d;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < GU; ++u) {
-            if (!dst[u]) continue;
-            if (wide[u]) st4(dst[u], v[u]);
-            else *dst[u] = v[u].x;
-        }
-    }
+__device__ __forceinline__ void gather_picked(const lap_storage_desc &st, const Outs &o, int capacity, int s,
+                                              int batch, const int32_t *pick) {
+    gather_rows<8>(st, o, min(batch, UPD_THREADS), threadIdx.x, UPD_THREADS, [=](int b) {
+        return Draw{(long)s * batch + b, (long)s * (capacity + 1) + pick[b]};
+    });
 }
 
 __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_kernel(float *tree, float *maxp, int cap, int levels,
                                                                         int capacity, const int32_t *idx_in,
                                                                         const float *prio, int batch,
                                                                         const int32_t *size, lap_storage_desc st,
-                                                                        SampleRng rng, int32_t *idx_out,
-                                                                        float *o_state, float *o_action, float *o_next,
-                                                                        float *o_reward, float *o_not_done,
+                                                                        SampleRng rng, int32_t *idx_out, Outs o,
                                                                         TdPrio tp, bool gather) {
     const int s = blockIdx.x;
     float *T = stratum_tree(tree, s, cap);
     const int32_t *I = idx_in + (size_t)s * batch;
-    const float *P = prio + (size_t)s * batch;
     __shared__ float red[UPD_THREADS / 64];
     __shared__ int32_t li[UPD_THREADS];
     __shared__ float top[TOPN_US];
     __shared__ int32_t pick[UPD_THREADS];
     const unsigned long long call = *rng.counter;  // read before any workgroup can take the ticket
-    float mx = 0.0f;
-    for (int b0 = 0; b0 < batch; b0 += UPD_THREADS) {
-        const int nb = min(UPD_THREADS, batch - b0);
-        __syncthreads();
-        if ((int)threadIdx.x < nb) li[threadIdx.x] = I[b0 + threadIdx.x];
-        __syncthreads();
-        const int b = b0 + threadIdx.x;
-        if (b < batch) {
-            const int me = li[threadIdx.x];
-            bool last = true;
-            for (int k = threadIdx.x + 1; k < nb; ++k) last &= (li[k] != me);
-            for (int b2 = b0 + nb; b2 < batch; ++b2) last &= (I[b2] != me);
-            float pb;
-            if (tp.td) {
-                const long d = (long)s * batch + b;
-                pb = powf(fmaxf(fmaxf(tp.td[2 * d], tp.td[2 * d + 1]), tp.minp), tp.alpha);
-                if (tp.out) tp.out[d] = pb;
-            } else {
-                pb = P[b];
-            }
-            if (last) T[cap + me] = pb;
-            mx = fmaxf(mx, pb);
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    float mx = update_leaves(T, cap, I, batch, tp, prio + (size_t)s * batch, s, li);
+    mx = wave_max_to(red, mx);
     const bool staged = propagate_top<TOPN_US>(T, cap, levels, I, batch, top);
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, red[w]);
-        atomicMax(reinterpret_cast<int *>(maxp), __float_as_int(mx));
-    }
+    block_max_to(maxp, mx, red);
     // ---- the next batch of this stratum
     const int lim = staged ? min(TOPN_US, 2 * cap) : 0;
     auto node_at = [&](int node) { return node < lim ? top[node] : T[node]; };
@@ -1493,21 +1279,11 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_kernel(float *t
         if (b < UPD_THREADS) pick[b] = i;
     }
     __syncthreads();
-    if (!gather) {  // the rows follow in lap_gather_kernel; the call counter's ticket below
-        if (threadIdx.x == 0 && atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
-            *rng.counter = call + 1ull;
-            *rng.ticket = 0u;
-        }
-        return;
+    if (gather) {  // (else the rows follow in lap_gather_kernel)
+        gather_picked(st, o, capacity, s, batch, pick);
+        __syncthreads();
     }
-    gather_picked(st, capacity, s, batch, pick, o_state, o_action, o_next, o_reward, o_not_done);
-    __syncthreads();
-    if (threadIdx.x == 0) {  // `call` was read (and used) before this add: no fence needed
-        if (atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
-            *rng.counter = call + 1ull;
-            *rng.ticket = 0u;
-        }
-    }
+    if (threadIdx.x == 0) rng_ticket(rng, call);  // `call` was read (and used) before this add: no fence needed
 }
 
 // lap_update_sample_kernel with its dependent global-memory round trips
@@ -1563,8 +1339,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_chain_kernel(
     float *tree, float *maxp, int cap, int levels, int capacity, const int32_t *idx_in,
     const float *__restrict__ prio, int batch, const int32_t *__restrict__ size, lap_storage_desc st, SampleRng rng,
-    int32_t *idx_out, float *o_state, float *o_action, float *o_next, float *o_reward, float *o_not_done, TdPrio tp,
-    bool gather) {
+    int32_t *idx_out, Outs o, TdPrio tp, bool gather) {
     const int s = blockIdx.x, t = threadIdx.x;
     float *T = stratum_tree(tree, s, cap);
     __shared__ float red[UPD_THREADS / 64];
@@ -1731,14 +1506,11 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_chain_kernel(
     }
     __syncthreads();
     if (gather) {
-        gather_picked(st, capacity, s, batch, pick, o_state, o_action, o_next, o_reward, o_not_done);
+        gather_picked(st, o, capacity, s, batch, pick);
         __syncthreads();
     }
     // ---- trip 5; `call` was read (and used) before this add: no fence needed
-    if (t == 0 && atomicAdd(rng.ticket, 1u) == gridDim.x - 1) {
-        *rng.counter = call + 1ull;
-        *rng.ticket = 0u;
-    }
+    if (t == 0) rng_ticket(rng, call);
 }
 
 int rc(hipError_t e) { return e == hipSuccess ? EXO_OK : EXO_EDEVICE; }
@@ -1751,11 +1523,12 @@ int levels_of(const lap_tree_desc *t) {
 
 // lap_update_sample's rows gathered by lap_gather_kernel (EXO_LAP_GATHER_SPLIT=0:
 // by the update's own stratum workgroups, the r04 layout)
+bool env_not_zero(const char *name) {  // unset, or not "0..."
+    const char *e = getenv(name);
+    return !(e && e[0] == '0');
+}
 bool gather_split() {
-    static const bool on = [] {
-        const char *e = getenv("EXO_LAP_GATHER_SPLIT");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = env_not_zero("EXO_LAP_GATHER_SPLIT");
     return on;
 }
 
@@ -1763,31 +1536,34 @@ bool gather_split() {
 // stratum (EXO_LAP_CHAIN=0: always lap_update_sample_kernel, the level sweeps;
 // read per call, the parity test switches it).  Both compute the same bits.
 void launch_update_sample(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *idx_in, const float *prio,
-                          int batch, SampleRng rng, int32_t *idx_out, float *o_state, float *o_action, float *o_next,
-                          float *o_reward, float *o_not_done, TdPrio tp, bool gather, void *stream) {
-    const char *e = getenv("EXO_LAP_CHAIN");
+                          int batch, SampleRng rng, int32_t *idx_out, const Outs &o, TdPrio tp, bool gather,
+                          void *stream) {
     const int levels = levels_of(t);
-    const bool chain = !(e && e[0] == '0') && batch <= CHAIN_MAXB && levels >= 1 &&
+    const bool chain = env_not_zero("EXO_LAP_CHAIN") && batch <= CHAIN_MAXB && levels >= 1 &&
                        lap_chain::global_levels(levels, TOPN_US) <= CHAIN_MAXG;
     if (chain)
         hipLaunchKernelGGL(lap_update_sample_chain_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels, t->capacity, idx_in, prio, batch, st->size, *st,
-                           rng, idx_out, o_state, o_action, o_next, o_reward, o_not_done, tp, gather);
+                           rng, idx_out, o, tp, gather);
     else
         hipLaunchKernelGGL(lap_update_sample_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels, t->capacity, idx_in, prio, batch, st->size, *st,
-                           rng, idx_out, o_state, o_action, o_next, o_reward, o_not_done, tp, gather);
+                           rng, idx_out, o, tp, gather);
 }
 
-int gather_after(const lap_tree_desc *t, const lap_storage_desc *st, int batch, const int32_t *idx, float *o_state,
-                 float *o_action, float *o_next, float *o_reward, float *o_not_done, void *stream) {
-    if (hipGetLastError() != hipSuccess) return EXO_EDEVICE;
-    if (!gather_split()) return EXO_OK;
+int launch_gather(const lap_tree_desc *t, const lap_storage_desc *st, int batch, const int32_t *idx, const Outs &o,
+                  void *stream) {
     const int total = t->n_strata * batch;
     hipLaunchKernelGGL(lap_gather_kernel, dim3((total + GATHER_DRAWS - 1) / GATHER_DRAWS), dim3(256), 0,
-                       (hipStream_t)stream, *st, t->capacity, idx, batch, total, o_state, o_action, o_next, o_reward,
-                       o_not_done);
-    return hipGetLastError() == hipSuccess ? EXO_OK : EXO_EDEVICE;
+                       (hipStream_t)stream, *st, t->capacity, idx, batch, total, o);
+    return rc(hipGetLastError());
+}
+
+int gather_after(const lap_tree_desc *t, const lap_storage_desc *st, int batch, const int32_t *idx, const Outs &o,
+                 void *stream) {
+    if (hipGetLastError() != hipSuccess) return EXO_EDEVICE;
+    if (!gather_split()) return EXO_OK;
+    return launch_gather(t, st, batch, idx, o, stream);
 }
 
 bool valid(const lap_tree_desc *t) {
@@ -1795,6 +1571,19 @@ bool valid(const lap_tree_desc *t) {
     return t && t->tree && t->max_priority && t->n_strata > 0 && t->capacity > 0 && t->cap >= t->capacity &&
            (t->cap & (t->cap - 1)) == 0 && t->cap <= (1 << MAXLV);
 }
+
+bool storage_ok(const lap_storage_desc *st) {  // the five row arrays
+    return st && st->state && st->action && st->next_state && st->reward && st->not_done;
+}
+bool rows_ok(const Rows &in) {
+    return in.state && in.action && in.next_state && in.reward && in.done && in.action_scale != 0.0f;
+}
+// what the three inserts (lap_store_batch, lap_store_batch_ref, the fused ref insert) all require
+bool store_args_ok(const lap_tree_desc *t, const lap_storage_desc *st, const Rows &in, const int32_t *strata, int n) {
+    return valid(t) && storage_ok(st) && st->size && st->state_dim > 0 && st->action_dim > 0 && rows_ok(in) &&
+           strata && n >= 0;
+}
+bool outs_ok(const Outs &o) { return o.state && o.action && o.next_state && o.reward && o.not_done; }
 
 } // namespace
 
@@ -1856,35 +1645,9 @@ int lap_totals(const lap_tree_desc *t, float *out, void *stream) {
 int lap_store_batch(const lap_tree_desc *t, const lap_storage_desc *st, const float *state, const float *action,
                     const float *next_state, const float *reward, const uint8_t *done, const int32_t *strata,
                     const uint8_t *active, float action_scale, int32_t n, int32_t *row_ws, void *stream) {
-    if (!valid(t) || !st || !st->state || !st->action || !st->next_state || !st->reward || !st->not_done ||
-        !st->ptr || !st->size || st->state_dim <= 0 || st->action_dim <= 0 || !state || !action || !next_state ||
-        !reward || !done || !strata || !row_ws || n < 0 || action_scale == 0.0f)
-        return EXO_EINVAL;
+    const Rows in{state, action, next_state, reward, done, action_scale};
+    if (!store_args_ok(t, st, in, strata, n) || !st->ptr || !row_ws) return EXO_EINVAL;
     if (n == 0) return EXO_OK;
-    // the one-launch insert (lap_store_fused_kernel) measured slower inside the
-    // training loop -- 0.2767-0.2771 vs 0.2522-0.2529 ms per iteration
-    // (profiles/r05_sched/r05s2): one workgroup per stratum copying its rows is
-    // slower than 1,024 copy workgroups -- so EXO_LAP_STORE_FUSED=1 opts in
-    // (read per call: the parity test switches it)
-    const char *fused_var = getenv("EXO_LAP_STORE_FUSED");
-    const bool fused_env = fused_var && fused_var[0] == '1';
-    if (fused_env && n <= STORE_FUSED_MAX && n <= t->capacity) {  // (no ring wrap inside one call)
-        const bool vec = (st->state_dim & 3) == 0 &&
-                         ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(next_state) |
-                           reinterpret_cast<uintptr_t>(st->state) | reinterpret_cast<uintptr_t>(st->next_state)) &
-                          15) == 0;
-        if (vec)
-            hipLaunchKernelGGL(lap_store_fused_kernel<true>, dim3(t->n_strata), dim3(UPD_THREADS), 0,
-                               (hipStream_t)stream, t->tree, t->max_priority, t->cap, levels_of(t), t->capacity,
-                               st->ptr, st->size, strata, active, n, row_ws, *st, state, action, next_state, reward,
-                               done, action_scale);
-        else
-            hipLaunchKernelGGL(lap_store_fused_kernel<false>, dim3(t->n_strata), dim3(UPD_THREADS), 0,
-                               (hipStream_t)stream, t->tree, t->max_priority, t->cap, levels_of(t), t->capacity,
-                               st->ptr, st->size, strata, active, n, row_ws, *st, state, action, next_state, reward,
-                               done, action_scale);
-        return rc(hipGetLastError());
-    }
     if (n > 4 * STORE_CHUNK)
         hipLaunchKernelGGL(lap_store_rank_kernel<16>, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, st->ptr, st->size, strata,
@@ -1894,8 +1657,8 @@ int lap_store_batch(const lap_tree_desc *t, const lap_storage_desc *st, const fl
                            t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, st->ptr, st->size, strata,
                            active, n, row_ws);
     if (hipGetLastError() != hipSuccess) return EXO_EDEVICE;
-    hipLaunchKernelGGL(lap_store_copy_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, state,
-                       action, next_state, reward, done, action_scale, n, row_ws);
+    hipLaunchKernelGGL(lap_store_copy_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, in, n,
+                       row_ws);
     return rc(hipGetLastError());
 }
 
@@ -1903,10 +1666,8 @@ int lap_store_batch_ref(const lap_tree_desc *t, const lap_storage_desc *st, int6
                         const float *action, const float *next_state, const float *reward, const uint8_t *done,
                         const int32_t *strata, const uint8_t *active, float action_scale, int32_t n,
                         int32_t *ws_dev, void *stream) {
-    if (!valid(t) || !st || !st->state || !st->action || !st->next_state || !st->reward || !st->not_done ||
-        !st->size || st->state_dim <= 0 || st->action_dim <= 0 || !ref_dev || !state || !action || !next_state ||
-        !reward || !done || !strata || !ws_dev || n < 0 || action_scale == 0.0f)
-        return EXO_EINVAL;
+    const Rows in{state, action, next_state, reward, done, action_scale};
+    if (!store_args_ok(t, st, in, strata, n) || !ref_dev || !ws_dev) return EXO_EINVAL;
     if (n == 0) return EXO_OK;
     int32_t *rank_row = ws_dev, *slot_of = ws_dev + n, *row_of = ws_dev + 2 * n;
     hipLaunchKernelGGL(lap_store_ref_slots_kernel, dim3(1), dim3(UPD_THREADS), 0, (hipStream_t)stream, t->capacity,
@@ -1915,36 +1676,27 @@ int lap_store_batch_ref(const lap_tree_desc *t, const lap_storage_desc *st, int6
     hipLaunchKernelGGL(lap_add_kernel, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream, t->tree,
                        t->max_priority, t->cap, levels_of(t), t->capacity, strata, slot_of, n);
     if (hipGetLastError() != hipSuccess) return EXO_EDEVICE;
-    hipLaunchKernelGGL(lap_store_copy_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, state,
-                       action, next_state, reward, done, action_scale, n, row_of);
+    hipLaunchKernelGGL(lap_store_copy_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, in, n,
+                       row_of);
     return rc(hipGetLastError());
 }
 
-static int store_ref_fused(const lap_tree_desc *t, const lap_storage_desc *st, int64_t *ref_dev,
-                           const float *state, const float *action, const float *next_state, const float *reward,
-                           const uint8_t *done, const int32_t *strata, const uint8_t *active, float action_scale,
-                           int32_t n, uint32_t *ticket_dev, const MaskAdvance &adv, void *stream) {
-    if (!valid(t) || !st || !st->state || !st->action || !st->next_state || !st->reward || !st->not_done ||
-        !st->size || st->state_dim <= 0 || st->action_dim <= 0 || !ref_dev || !state || !action || !next_state ||
-        !reward || !done || !strata || !ticket_dev || n < 0 || action_scale == 0.0f)
-        return EXO_EINVAL;
+static int store_ref_fused(const lap_tree_desc *t, const lap_storage_desc *st, int64_t *ref_dev, const Rows &in,
+                           const int32_t *strata, const uint8_t *active, int32_t n, uint32_t *ticket_dev,
+                           const MaskAdvance &adv, void *stream) {
+    if (!store_args_ok(t, st, in, strata, n) || !ref_dev || !ticket_dev) return EXO_EINVAL;
     if (n == 0) return EXO_OK;
     const int E = t->n_strata;
     // part 0 of a stratum: leaves + ancestors; parts 1..K-1: ~64 rows of the copy each
     const int K = 1 + std::max(1, std::min(15, (n + E * 64 - 1) / (E * 64)));
-    auto al16 = [](const void *p) { return ((uintptr_t)p & 15u) == 0; };
-    const bool vec = st->state_dim % 4 == 0 && al16(state) && al16(next_state) && al16(st->state) &&
-                     al16(st->next_state);
-    if (vec)
+    if (rows_vec(*st, in.state, in.next_state))
         hipLaunchKernelGGL(lap_store_ref_fused_kernel<true>, dim3(E, K), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, E, (long long *)ref_dev,
-                           st->size, *st, state, action, next_state, reward, done, action_scale, strata, active, n,
-                           ticket_dev, adv);
+                           st->size, *st, in, strata, active, n, ticket_dev, adv);
     else
         hipLaunchKernelGGL(lap_store_ref_fused_kernel<false>, dim3(E, K), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, E, (long long *)ref_dev,
-                           st->size, *st, state, action, next_state, reward, done, action_scale, strata, active, n,
-                           ticket_dev, adv);
+                           st->size, *st, in, strata, active, n, ticket_dev, adv);
     return rc(hipGetLastError());
 }
 
@@ -1952,8 +1704,8 @@ int lap_store_batch_ref_fused(const lap_tree_desc *t, const lap_storage_desc *st
                               const float *state, const float *action, const float *next_state, const float *reward,
                               const uint8_t *done, const int32_t *strata, const uint8_t *active, float action_scale,
                               int32_t n, uint32_t *ticket_dev, void *stream) {
-    return store_ref_fused(t, st, ref_dev, state, action, next_state, reward, done, strata, active, action_scale, n,
-                           ticket_dev, MaskAdvance{}, stream);
+    return store_ref_fused(t, st, ref_dev, Rows{state, action, next_state, reward, done, action_scale}, strata, active,
+                           n, ticket_dev, MaskAdvance{}, stream);
 }
 
 int lap_store_batch_ref_fused_adv(const lap_tree_desc *t, const lap_storage_desc *st, int64_t *ref_dev,
@@ -1962,21 +1714,20 @@ int lap_store_batch_ref_fused_adv(const lap_tree_desc *t, const lap_storage_desc
                                   float action_scale, int32_t n, uint32_t *ticket_dev, const uint8_t *table,
                                   int32_t rows, int64_t *k_dev, int32_t *count_dev, double *score_dev, void *stream) {
     if (!table || rows <= 0 || !k_dev || !active) return EXO_EINVAL;
-    return store_ref_fused(t, st, ref_dev, state, action, next_state, reward, done, strata, active, action_scale, n,
-                           ticket_dev, MaskAdvance{table, rows, (long long *)k_dev, active, count_dev, score_dev},
+    return store_ref_fused(t, st, ref_dev, Rows{state, action, next_state, reward, done, action_scale}, strata, active,
+                           n, ticket_dev, MaskAdvance{table, rows, (long long *)k_dev, active, count_dev, score_dev},
                            stream);
 }
 
 int lap_sample_gather(const lap_tree_desc *t, const lap_storage_desc *st, const float *u, int32_t batch,
                       int32_t *idx, float *out_state, float *out_action, float *out_next_state, float *out_reward,
                       float *out_not_done, void *stream) {
-    if (!valid(t) || !st || !st->size || !u || !idx || batch <= 0 || !out_state || !out_action ||
-        !out_next_state || !out_reward || !out_not_done)
-        return EXO_EINVAL;
+    const Outs o{out_state, out_action, out_next_state, out_reward, out_not_done};
+    if (!valid(t) || !st || !st->size || !u || !idx || batch <= 0 || !outs_ok(o)) return EXO_EINVAL;
     const int total = t->n_strata * batch;
     hipLaunchKernelGGL(lap_sample_gather_kernel, dim3((total + 3) / 4), dim3(256), 0, (hipStream_t)stream, t->tree,
-                       t->cap, levels_of(t), t->capacity, u, st->size, batch, total, idx, *st, out_state, out_action,
-                       out_next_state, out_reward, out_not_done, SampleRng{0, 0, nullptr, nullptr});
+                       t->cap, levels_of(t), t->capacity, u, st->size, batch, total, idx, *st, o,
+                       SampleRng{0, 0, nullptr, nullptr});
     return rc(hipGetLastError());
 }
 
@@ -1984,13 +1735,13 @@ int lap_update_sample_rng(const lap_tree_desc *t, const lap_storage_desc *st, co
                           const float *prio, int32_t batch, uint64_t seed, uint32_t tag, unsigned long long *counter,
                           uint32_t *ticket, int32_t *idx_out, float *out_state, float *out_action,
                           float *out_next_state, float *out_reward, float *out_not_done, void *stream) {
+    const Outs o{out_state, out_action, out_next_state, out_reward, out_not_done};
     if (!valid(t) || !st || !st->size || !idx_in || !prio || !counter || !ticket || !idx_out || batch <= 0 ||
-        batch > UPD_THREADS || !out_state || !out_action || !out_next_state || !out_reward || !out_not_done)
+        batch > UPD_THREADS || !outs_ok(o))
         return EXO_EINVAL;
-    launch_update_sample(t, st, idx_in, prio, batch, SampleRng{seed, tag, counter, ticket}, idx_out, out_state,
-                         out_action, out_next_state, out_reward, out_not_done, TdPrio{nullptr, 0.f, 0.f, nullptr},
-                         !gather_split(), stream);
-    return gather_after(t, st, batch, idx_out, out_state, out_action, out_next_state, out_reward, out_not_done, stream);
+    launch_update_sample(t, st, idx_in, prio, batch, SampleRng{seed, tag, counter, ticket}, idx_out, o,
+                         TdPrio{nullptr, 0.f, 0.f, nullptr}, !gather_split(), stream);
+    return gather_after(t, st, batch, idx_out, o, stream);
 }
 
 int lap_update_sample_idx(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *idx_in,
@@ -1999,22 +1750,17 @@ int lap_update_sample_idx(const lap_tree_desc *t, const lap_storage_desc *st, co
     if (!valid(t) || !st || !st->size || !idx_in || !prio || !counter || !ticket || !idx_out || batch <= 0 ||
         batch > UPD_THREADS)
         return EXO_EINVAL;
-    launch_update_sample(t, st, idx_in, prio, batch, SampleRng{seed, tag, counter, ticket}, idx_out, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, TdPrio{nullptr, 0.f, 0.f, nullptr}, false, stream);
+    launch_update_sample(t, st, idx_in, prio, batch, SampleRng{seed, tag, counter, ticket}, idx_out, Outs{},
+                         TdPrio{nullptr, 0.f, 0.f, nullptr}, false, stream);
     return rc(hipGetLastError());
 }
 
 int lap_gather_rows(const lap_tree_desc *t, const lap_storage_desc *st, int32_t batch, const int32_t *idx,
                     float *out_state, float *out_action, float *out_next_state, float *out_reward,
                     float *out_not_done, void *stream) {
-    if (!valid(t) || !st || !st->state || !st->action || !st->next_state || !st->reward || !st->not_done || !idx ||
-        batch <= 0 || !out_state || !out_action || !out_next_state || !out_reward || !out_not_done)
-        return EXO_EINVAL;
-    const int total = t->n_strata * batch;
-    hipLaunchKernelGGL(lap_gather_kernel, dim3((total + GATHER_DRAWS - 1) / GATHER_DRAWS), dim3(256), 0,
-                       (hipStream_t)stream, *st, t->capacity, idx, batch, total, out_state, out_action,
-                       out_next_state, out_reward, out_not_done);
-    return rc(hipGetLastError());
+    const Outs o{out_state, out_action, out_next_state, out_reward, out_not_done};
+    if (!valid(t) || !storage_ok(st) || !idx || batch <= 0 || !outs_ok(o)) return EXO_EINVAL;
+    return launch_gather(t, st, batch, idx, o, stream);
 }
 
 int lap_update_sample_td(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *idx_in, const float *td,
@@ -2022,26 +1768,25 @@ int lap_update_sample_td(const lap_tree_desc *t, const lap_storage_desc *st, con
                          unsigned long long *counter, uint32_t *ticket, int32_t *idx_out, float *out_state,
                          float *out_action, float *out_next_state, float *out_reward, float *out_not_done,
                          void *stream) {
+    const Outs o{out_state, out_action, out_next_state, out_reward, out_not_done};
     if (!valid(t) || !st || !st->size || !idx_in || !td || !counter || !ticket || !idx_out || batch <= 0 ||
-        batch > UPD_THREADS || !out_state || !out_action || !out_next_state || !out_reward || !out_not_done)
+        batch > UPD_THREADS || !outs_ok(o))
         return EXO_EINVAL;
-    launch_update_sample(t, st, idx_in, nullptr, batch, SampleRng{seed, tag, counter, ticket}, idx_out, out_state,
-                         out_action, out_next_state, out_reward, out_not_done,
+    launch_update_sample(t, st, idx_in, nullptr, batch, SampleRng{seed, tag, counter, ticket}, idx_out, o,
                          TdPrio{td, alpha, min_priority, prio_out}, !gather_split(), stream);
-    return gather_after(t, st, batch, idx_out, out_state, out_action, out_next_state, out_reward, out_not_done, stream);
+    return gather_after(t, st, batch, idx_out, o, stream);
 }
 
 int lap_sample_gather_rng(const lap_tree_desc *t, const lap_storage_desc *st, uint64_t seed, uint32_t tag,
                           unsigned long long *counter, uint32_t *ticket, int32_t batch, int32_t *idx,
                           float *out_state, float *out_action, float *out_next_state, float *out_reward,
                           float *out_not_done, void *stream) {
-    if (!valid(t) || !st || !st->size || !counter || !ticket || !idx || batch <= 0 || !out_state || !out_action ||
-        !out_next_state || !out_reward || !out_not_done)
-        return EXO_EINVAL;
+    const Outs o{out_state, out_action, out_next_state, out_reward, out_not_done};
+    if (!valid(t) || !st || !st->size || !counter || !ticket || !idx || batch <= 0 || !outs_ok(o)) return EXO_EINVAL;
     const int total = t->n_strata * batch;
     hipLaunchKernelGGL(lap_sample_gather_kernel, dim3((total + 3) / 4), dim3(256), 0, (hipStream_t)stream, t->tree,
-                       t->cap, levels_of(t), t->capacity, nullptr, st->size, batch, total, idx, *st, out_state,
-                       out_action, out_next_state, out_reward, out_not_done, SampleRng{seed, tag, counter, ticket});
+                       t->cap, levels_of(t), t->capacity, nullptr, st->size, batch, total, idx, *st, o,
+                       SampleRng{seed, tag, counter, ticket});
     return rc(hipGetLastError());
 }
 
@@ -2068,15 +1813,13 @@ int lap_ref_step(const lap_tree_desc *t, const lap_storage_desc *st, const int32
                  const float *state, const float *action, const float *next_state, const float *reward,
                  const uint8_t *done, float action_scale, const uint8_t *table_dev, uint8_t *active_dev,
                  int32_t *count_dev, const int32_t *counts_table_dev, double *score_dev, void *stream) {
-    if (!valid(t) || !st || !st->state || !st->action || !st->next_state || !st->reward || !st->not_done ||
-        !plan_dev || rows <= 0 || n <= 0 || !kk_dev || (par != 0 && par != 1) || !strata_dev || !state || !action ||
-        !next_state || !reward || !done || action_scale == 0.0f || !table_dev || !active_dev ||
-        (count_dev && !counts_table_dev))
+    const Rows in{state, action, next_state, reward, done, action_scale};
+    if (!valid(t) || !storage_ok(st) || !plan_dev || rows <= 0 || n <= 0 || !kk_dev || (par != 0 && par != 1) ||
+        !strata_dev || !rows_ok(in) || !table_dev || !active_dev || (count_dev && !counts_table_dev))
         return EXO_EINVAL;
     hipLaunchKernelGGL(lap_ref_step_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, plan_dev,
-                       rows, n, (long long *)kk_dev, par, (long long *)k_dev, strata_dev, t->capacity, state, action,
-                       next_state, reward, done, action_scale, table_dev, active_dev, count_dev, counts_table_dev,
-                       score_dev);
+                       rows, n, (long long *)kk_dev, par, (long long *)k_dev, strata_dev, t->capacity, in, table_dev,
+                       active_dev, count_dev, counts_table_dev, score_dev);
     return rc(hipGetLastError());
 }
 

@@ -128,6 +128,29 @@ class LAP:
         self.count += 1
         self.size_s.fill_(self.size)
 
+    def _step_args(self, state, action, next_state, reward, done, strata, active):
+        """One env step's tensors as the insert kernels read them: contiguous
+        float32 rows, done and active as uint8 (a bool or uint8 mask is viewed,
+        not copied: an in-place mask stays the caller's), strata as int32."""
+        n = state.shape[0]
+
+        def f32(t, shape):
+            t = t.to(device=self.device, dtype=torch.float32).reshape(shape)
+            return t if t.is_contiguous() else t.contiguous()
+
+        def u8(t):
+            return t if t.dtype == torch.uint8 else (t.view(torch.uint8) if t.dtype == torch.bool
+                                                     else t.to(torch.uint8))
+
+        st = f32(state, (n, self.state_dim))
+        nx = f32(next_state, (n, self.state_dim))
+        ac = f32(action, (n, self.action_dim))
+        rw = f32(reward, (n,))
+        dn = u8(done).reshape(n).contiguous()
+        sr = (strata if strata.dtype == torch.int32 else strata.to(torch.int32)).contiguous()
+        act = None if active is None else u8(active).contiguous()
+        return st, ac, nx, rw, dn, sr, act
+
     def add_batch(self, state, action, next_state, reward, done, strata, active=None):
         """One vectorised env step: row i goes to stratum strata[i] (int32 [N]) if
         active[i] (bool/uint8 [N], default all) -- lap_store_batch, two kernels,
@@ -135,25 +158,9 @@ class LAP:
         n = state.shape[0]
         if self._row_ws is None or self._row_ws.numel() < n:
             self._row_ws = torch.empty((n,), dtype=torch.int32, device=self.device)
-
-        def f32(t, shape):
-            t = t.to(device=self.device, dtype=torch.float32).reshape(shape)
-            return t if t.is_contiguous() else t.contiguous()
-
-        st = f32(state, (n, self.state_dim))
-        nx = f32(next_state, (n, self.state_dim))
-        ac = f32(action, (n, self.action_dim))
-        rw = f32(reward, (n,))
-        dn = done if done.dtype == torch.uint8 else (done.view(torch.uint8) if done.dtype == torch.bool
-                                                     else done.to(torch.uint8))
-        dn = dn.reshape(n).contiguous()
-        sr = strata if strata.dtype == torch.int32 else strata.to(torch.int32)
-        act = None
-        if active is not None:
-            act = active.view(torch.uint8) if active.dtype == torch.bool else active.to(torch.uint8)
-            act = act.contiguous()
+        st, ac, nx, rw, dn, sr, act = self._step_args(state, action, next_state, reward, done, strata, active)
         nat.check(nat.lib().lap_store_batch(ctypes.byref(self._desc), ctypes.byref(self._store), nat.ptr(st),
-                                            nat.ptr(ac), nat.ptr(nx), nat.ptr(rw), nat.ptr(dn), nat.ptr(sr.contiguous()),
+                                            nat.ptr(ac), nat.ptr(nx), nat.ptr(rw), nat.ptr(dn), nat.ptr(sr),
                                             nat.ptr(act), float(self.normalize_actions), n, nat.ptr(self._row_ws),
                                             self._stream()), "lap_store_batch")
 
@@ -236,22 +243,7 @@ class LAP:
         if self._ref_ws is None or self._ref_ws.numel() < 3 * n:
             # zeroed: its first word is the fused launch's ticket (left zero)
             self._ref_ws = torch.zeros((3 * n,), dtype=torch.int32, device=self.device)
-
-        def f32(t, shape):
-            t = t.to(device=self.device, dtype=torch.float32).reshape(shape)
-            return t if t.is_contiguous() else t.contiguous()
-
-        st = f32(state, (n, self.state_dim))
-        nx = f32(next_state, (n, self.state_dim))
-        ac = f32(action, (n, self.action_dim))
-        rw = f32(reward, (n,))
-        dn = done if done.dtype == torch.uint8 else (done.view(torch.uint8) if done.dtype == torch.bool
-                                                     else done.to(torch.uint8))
-        dn = dn.reshape(n).contiguous()
-        sr = (strata if strata.dtype == torch.int32 else strata.to(torch.int32)).contiguous()
-        act = None
-        if active is not None:
-            act = (active.view(torch.uint8) if active.dtype == torch.bool else active.to(torch.uint8)).contiguous()
+        st, ac, nx, rw, dn, sr, act = self._step_args(state, action, next_state, reward, done, strata, active)
         if advance is not None:
             if not self.ref_insert_fused or act is None or act.data_ptr() != active.data_ptr():
                 raise ValueError("add_batch_ref(advance=...): the fused insert and an in-place uint8/bool mask only")

@@ -10,9 +10,9 @@ from helpers import GOLDEN
 pytestmark = pytest.mark.gpu
 
 
-def _lap(E, size, batch):
+def _lap(E, size, batch, state_dim=80):
     from exo_amd.replay import LAP
-    return LAP(80, 7, "cuda", E, max_size=size, batch_size=batch)
+    return LAP(state_dim, 7, "cuda", E, max_size=size, batch_size=batch)
 
 
 def _set_priorities(lap, prio):
@@ -103,29 +103,41 @@ def test_reference_single_add_pointer_semantics():
     assert lap.ptr == 2 and lap.size == 2 and lap.count == 6
 
 
-def test_sample_gathers_the_rows_of_its_indices():
+def _old(*values):
+    """A case from before the state_dim parameter (80), under the id it had."""
+    return pytest.param(*values, 80, id="-".join(str(v) for v in values))
+
+
+@pytest.mark.parametrize("E,B,sd", [(3, 5, 6)])
+def test_sample_gathers_the_rows_of_its_indices_scalar_rows(E, B, sd):
+    """The test below with rows that are no multiple of 16 bytes (the scalar
+    copies), 15 draws."""
+    test_sample_gathers_the_rows_of_its_indices(E, B, sd)
+
+
+def test_sample_gathers_the_rows_of_its_indices(E=4, B=16, sd=80):
     """lap_sample_gather: the returned batch is the storage rows at lap.ind
     (stratum-major), with action scaled and not_done = 1 - done as stored."""
-    lap = _lap(4, 64, 16)
+    lap = _lap(E, 64, B, sd)
     n = 200
     g = torch.Generator(device="cuda").manual_seed(1)
-    strata = torch.randint(0, 4, (n,), device="cuda", dtype=torch.int32, generator=g)
+    strata = torch.randint(0, E, (n,), device="cuda", dtype=torch.int32, generator=g)
     for step in range(3):
-        obs = torch.randn(n, 80, device="cuda", generator=g)
+        obs = torch.randn(n, sd, device="cuda", generator=g)
         act = torch.rand(n, 7, device="cuda", generator=g) * 2 - 1
         done = (torch.rand(n, device="cuda", generator=g) < 0.3).to(torch.uint8)
         lap.add_batch(obs, act, obs + 1, torch.randn(n, device="cuda", generator=g), done, strata)
     s, a, ns, r, nd = lap.sample()
     idx = lap.ind.long()
-    rows = (torch.arange(4, device="cuda")[:, None] * 65 + idx).reshape(-1)
-    torch.testing.assert_close(s, lap.state.view(-1, 80)[rows], rtol=0, atol=0)
+    rows = (torch.arange(E, device="cuda")[:, None] * 65 + idx).reshape(-1)
+    torch.testing.assert_close(s, lap.state.view(-1, sd)[rows], rtol=0, atol=0)
     torch.testing.assert_close(a, lap.action.view(-1, 7)[rows], rtol=0, atol=0)
-    torch.testing.assert_close(ns, lap.next_state.view(-1, 80)[rows], rtol=0, atol=0)
+    torch.testing.assert_close(ns, lap.next_state.view(-1, sd)[rows], rtol=0, atol=0)
     torch.testing.assert_close(r, lap.reward.view(-1, 1)[rows], rtol=0, atol=0)
     torch.testing.assert_close(nd, lap.not_done.view(-1, 1)[rows], rtol=0, atol=0)
     assert int(idx.max()) < 64 and set(torch.unique(nd).tolist()) <= {0.0, 1.0}
     sizes = lap.size_s.cpu().numpy()
-    assert all(int(idx[k].max()) < sizes[k] for k in range(4))
+    assert all(int(idx[k].max()) < sizes[k] for k in range(E))
 
 
 def test_sample_matches_reference_at_full_depth():
@@ -181,21 +193,21 @@ def test_sample_never_returns_the_slot_at_size():
     assert set(np.unique(idx[1])) == set(np.unique(idx[2])) == {1, 2, 3, 4}
 
 
-@pytest.mark.parametrize("fused", [True, False])
-def test_add_batch_ref_equals_sequential_reference_adds(fused):
+@pytest.mark.parametrize("fused,sd", [_old(True), _old(False), (True, 6), (False, 6)])
+def test_add_batch_ref_equals_sequential_reference_adds(fused, sd):
     """lap_store_batch_ref (fused: the one-launch lap_store_batch_ref_fused) ==
     LAP.add (:49-63) called once per active row in row order: stored
     transitions, leaves, sums, the shared pointer and size -- random strata
     (several rows per stratum), random active masks (overwrites of one slot by
     two adds of a stratum between pointer advances: the later add wins), a
-    pointer that wraps the capacity."""
+    pointer that wraps the capacity; sd = 6: the scalar row copies."""
     rng = np.random.default_rng(3)
     E, C, N = 4, 40, 19
-    seq, vec = _lap(E, C, 4), _lap(E, C, 4)
+    seq, vec = _lap(E, C, 4, sd), _lap(E, C, 4, sd)
     vec.ref_insert_fused = fused
     for step in range(30):
-        st = rng.normal(size=(N, 80)).astype(np.float32)
-        nx = rng.normal(size=(N, 80)).astype(np.float32)
+        st = rng.normal(size=(N, sd)).astype(np.float32)
+        nx = rng.normal(size=(N, sd)).astype(np.float32)
         ac = rng.uniform(-1, 1, (N, 7)).astype(np.float32)
         rw = rng.normal(size=N).astype(np.float32)
         dn = rng.random(N) < 0.1
@@ -218,17 +230,22 @@ def test_add_batch_ref_equals_sequential_reference_adds(fused):
     assert seq.count > 2 * C  # the pointer wrapped
 
 
-@pytest.mark.parametrize("E,C,N", [(8, 5000, 10_000), (8, 30_000, 4096), (5, 3000, 9001)])
-def test_fused_ref_insert_equals_three_launch_insert(E, C, N):
+@pytest.mark.parametrize("E,C,N,sd", [_old(8, 5000, 10_000), _old(8, 30_000, 4096), _old(5, 3000, 9001),
+                                      (3, 1400, 4099, 6)])
+def test_fused_ref_insert_equals_three_launch_insert(E, C, N, sd):
     """lap_store_batch_ref_fused (one launch, r04) against the three-launch
     lap_store_batch_ref (pinned to the sequential adds above) at the rollout's
     sizes: several 4,096-row chunks (a stratum's last row of a chunk decided by
     the next chunk), more copy parts than one, non-integer priorities already
     in the tree, masks with whole runs of done envs, ring wrap-around; the
     storage, every tree node, the shared pointer and the sizes bit for bit,
-    and every internal node exactly left + right."""
+    and every internal node exactly left + right.  (3, 1400, 4099, 6): the carry
+    row across a chunk edge with scalar copies, 21 items per row over K > 2
+    copy parts (no multiple of 4 x 1,024).  One call's adds must not wrap the
+    ring onto their own slots (N / E + 1 <= C): two winners of one slot would
+    be copied in either order, by both paths."""
     rng = np.random.default_rng(E * 1000 + N)
-    a, b = _lap(E, C, 64), _lap(E, C, 64)
+    a, b = _lap(E, C, 64, sd), _lap(E, C, 64, sd)
     a.ref_insert_fused, b.ref_insert_fused = False, True
     prio = rng.gamma(0.7, 2.0, (E, C)).astype(np.float32) + np.float32(1e-3)
     for lap in (a, b):
@@ -236,8 +253,8 @@ def test_fused_ref_insert_equals_three_launch_insert(E, C, N):
     T = lambda x: torch.as_tensor(x, device="cuda")  # noqa: E731
     strata = (np.arange(N) % E).astype(np.int32)
     for step in range(6):
-        st = rng.normal(size=(N, 80)).astype(np.float32)
-        nx = rng.normal(size=(N, 80)).astype(np.float32)
+        st = rng.normal(size=(N, sd)).astype(np.float32)
+        nx = rng.normal(size=(N, sd)).astype(np.float32)
         ac = rng.uniform(-1, 1, (N, 7)).astype(np.float32)
         rw = rng.normal(size=N).astype(np.float32)
         dn = rng.random(N) < 0.05
@@ -300,17 +317,20 @@ def test_fused_ref_insert_with_mask_advance_equals_two_launches():
         assert int(k_b) == min(step + 1, rows - 1)
 
 
-@pytest.mark.parametrize("C,B,size", [(30_000, 128, 30_000), (30_000, 128, 17_001), (40, 16, 40), (250_000, 64, 99)])
-def test_update_and_sample_in_one_launch_equals_two(C, B, size):
+@pytest.mark.parametrize("C,B,size,E,sd", [pytest.param(C, B, size, 8, 80, id=f"{C}-{B}-{size}") for C, B, size in
+                                           [(30_000, 128, 30_000), (30_000, 128, 17_001), (40, 16, 40),
+                                            (250_000, 64, 99)]] + [(40, 5, 33, 3, 6)])
+def test_update_and_sample_in_one_launch_equals_two(C, B, size, E, sd):
     """lap_update_sample_rng (r04): LAP.update_priority then the next sample in
     ONE launch -- the descent reading the top levels the update left in LDS --
     against update_priority() then sample(): every tree node, max_priority,
     the sampled indices and gathered rows, and the RNG call counter, bit for
     bit; non-integer priorities, duplicate update indices, sampling sizes below
-    the capacity (the prefix-total path), small and full-depth trees."""
-    E = 8
+    the capacity (the prefix-total path), small and full-depth trees.
+    (40, 5, 33, 3, 6): 15 draws -- a gather workgroup with fewer draws than it
+    holds -- of rows that are no multiple of 16 bytes (the scalar gather)."""
     rng = np.random.default_rng(C + B)
-    a, b = _lap(E, C, B), _lap(E, C, B)
+    a, b = _lap(E, C, B, sd), _lap(E, C, B, sd)
     prio = rng.gamma(0.7, 2.0, (E, C)).astype(np.float32) + np.float32(1e-3)
     for lap in (a, b):
         _set_priorities(lap, prio)
@@ -408,44 +428,51 @@ def test_store_span_propagation_keeps_the_tree_exact(C):
         np.testing.assert_array_equal(T[s, 1:cap], T[s, 2:2 * cap:2] + T[s, 3:2 * cap:2])
 
 
-@pytest.mark.parametrize("fused", ["0", "1"])
-@pytest.mark.parametrize("n,cap,steps", [(4096, 30000, 5), (1000, 2048, 9), (8192, 9000, 3)])
-def test_vectorised_insert_equals_per_row_ring_adds(n, cap, steps, fused, monkeypatch):
-    """lap_store_batch (r05: one launch up to 8,192 rows -- scan, leaves, span
-    propagation and the row copies in one workgroup per stratum) against the
+@pytest.mark.parametrize("n,cap,steps,sd", [_old(4096, 30000, 5), _old(1000, 2048, 9), _old(8192, 9000, 3),
+                                            (4099, 700, 3, 6), (16387, 2500, 2, 80)])
+def test_vectorised_insert_equals_per_row_ring_adds(n, cap, steps, sd):
+    """lap_store_batch (the rank launch -- scan, leaves, span propagation -- and
+    the row copies, one wavefront per row) against the
     per-stratum ring semantics row by row: rows of stratum s in env order to
     slots ptr_s, ptr_s + 1, ... (mod capacity), leaves = max_priority, every
     inner node the sum of its children; random masks and strata, ring wraps
-    across calls.  fused: the opt-in one-launch insert (EXO_LAP_STORE_FUSED=1,
-    measured slower in the loop) against the same semantics."""
-    monkeypatch.setenv("EXO_LAP_STORE_FUSED", fused)
+    across calls; all five stored columns of every slot.  (4099, 700, 3, 6):
+    two scan chunks with a ragged tail, ring wrap, scalar copies; (16387,
+    2500, 2, 80): 16 rows per thread, two chunks of them."""
     E = 8
-    lap = _lap(E, cap, 16)
+    lap = _lap(E, cap, 16, sd)
     g = torch.Generator(device="cuda").manual_seed(n + cap)
     strata = torch.randint(0, E, (n,), device="cuda", generator=g, dtype=torch.int32)
     ptr = np.zeros(E, dtype=np.int64)
     size = np.zeros(E, dtype=np.int64)
-    want_state = np.zeros((E, cap + 1), dtype=np.float32)
+    want = {"state": np.zeros((E, cap, sd), np.float32), "next_state": np.zeros((E, cap, sd), np.float32),
+            "action": np.zeros((E, cap, 7), np.float32), "reward": np.zeros((E, cap, 1), np.float32),
+            "not_done": np.zeros((E, cap, 1), np.float32)}
     st_h = strata.cpu().numpy()
     for k in range(steps):
         active = torch.rand(n, device="cuda", generator=g) < 0.8
-        obs = torch.randn(n, 80, device="cuda", generator=g)
-        nobs = torch.randn(n, 80, device="cuda", generator=g)
+        obs = torch.randn(n, sd, device="cuda", generator=g)
+        nobs = torch.randn(n, sd, device="cuda", generator=g)
         act = torch.rand(n, 7, device="cuda", generator=g) * 2 - 1
         rew = torch.randn(n, device="cuda", generator=g)
         done = torch.rand(n, device="cuda", generator=g) < 0.1
         lap.add_batch(obs, act, nobs, rew, done, strata, active)
-        a_h, o_h = active.cpu().numpy(), obs[:, 0].cpu().numpy()
+        a_h = active.cpu().numpy()
+        cols = {"state": obs.cpu().numpy(), "next_state": nobs.cpu().numpy(),
+                "action": act.cpu().numpy() / np.float32(lap.normalize_actions),
+                "reward": rew.cpu().numpy()[:, None], "not_done": 1.0 - done.cpu().numpy()[:, None].astype(np.float32)}
         for i in range(n):
             if a_h[i]:
                 s = st_h[i]
-                want_state[s, ptr[s]] = o_h[i]
+                for name, c in cols.items():
+                    want[name][s, ptr[s]] = c[i]
                 ptr[s] = (ptr[s] + 1) % cap
                 size[s] = min(size[s] + 1, cap)
     torch.cuda.synchronize()
     np.testing.assert_array_equal(lap.ptr_s.cpu().numpy(), ptr)
     np.testing.assert_array_equal(lap.size_s.cpu().numpy(), size)
-    np.testing.assert_array_equal(lap.state[:, :cap, 0].cpu().numpy(), want_state[:, :cap])
+    for name, w in want.items():
+        np.testing.assert_array_equal(getattr(lap, name)[:, :cap].cpu().numpy(), w, err_msg=name)
     tree = lap._tree.cpu().numpy().astype(np.float64)
     c2 = tree.shape[1] // 2
     for s in range(E):
@@ -454,9 +481,10 @@ def test_vectorised_insert_equals_per_row_ring_adds(n, cap, steps, fused, monkey
         assert tree[s, 1] == float(size[s])  # integer sums: exact at any order
 
 
-@pytest.mark.parametrize("E,C,n,rows,p_act", [(8, 40, 37, 9, 0.5), (8, 4096, 300, 12, 0.9), (4, 23, 11, 7, 0.15),
-                                             (8, 5000, 4096, 4, 0.97)])
-def test_planned_round_equals_per_step_reference_inserts(E, C, n, rows, p_act):
+@pytest.mark.parametrize("E,C,n,rows,p_act,sd", [_old(8, 40, 37, 9, 0.5), _old(8, 4096, 300, 12, 0.9),
+                                                _old(4, 23, 11, 7, 0.15), _old(8, 5000, 4096, 4, 0.97),
+                                                (4, 23, 11, 7, 0.15, 6)])
+def test_planned_round_equals_per_step_reference_inserts(E, C, n, rows, p_act, sd):
     """lap_ref_plan + lap_ref_step per row + lap_ref_commit (the reference
     schedule's planned rollout inserts, r05) against add_batch_ref per row (the
     per-step inserts, pinned to the sequential adds above): storage, every tree
@@ -465,7 +493,7 @@ def test_planned_round_equals_per_step_reference_inserts(E, C, n, rows, p_act):
     ptr0 + adv - 1 (count0 + total - 1 not a multiple of E), a
     round with fewer adds than E, an empty round and a ring that wraps."""
     rng = np.random.default_rng(C + n)
-    a, b = _lap(E, C, 16), _lap(E, C, 16)
+    a, b = _lap(E, C, 16, sd), _lap(E, C, 16, sd)
     T = lambda x: torch.as_tensor(x, device="cuda")  # noqa: E731
     strata = T(rng.integers(0, E, n).astype(np.int32))
     kk = torch.zeros((2,), dtype=torch.int64, device="cuda")
@@ -488,7 +516,7 @@ def test_planned_round_equals_per_step_reference_inserts(E, C, n, rows, p_act):
         b.ref_plan(tb, strata, offs, total, plan)
         active_b = tb[0].clone()
         for k in range(rows):
-            st, nx = T(rng.normal(size=(n, 80)).astype(np.float32)), T(rng.normal(size=(n, 80)).astype(np.float32))
+            st, nx = T(rng.normal(size=(n, sd)).astype(np.float32)), T(rng.normal(size=(n, sd)).astype(np.float32))
             ac = T(rng.uniform(-1, 1, (n, 7)).astype(np.float32))
             rw, dn = T(rng.normal(size=n).astype(np.float32)), T(rng.random(n) < 0.1)
             a.add_batch_ref(st, ac, nx, rw, dn, strata, tb[k])

@@ -1,7 +1,7 @@
 """LAP launch timings at the bench's shape (8 strata x 250,000 slots, 176,128
 transitions per stratum -- one 4,096-env episode round -- batch 8 x 128): the
-training loop's priority update + next sample (one launch), and the update /
-sample-gather launches alone.  Each launch captured 20x in a HIP graph, timed
+training loop's priority update + next sample (one launch), the update /
+sample-gather launches alone, and the two inserts.  Each launch captured 20x in a HIP graph, timed
 with HIP events over 10 replays.  usage: python tools/lap_bench.py"""
 import os
 import sys
@@ -71,8 +71,11 @@ def main():
 
     def ref_insert():
         rb2.add_batch_ref(obs, act, obs, rew, done, strata, active, advance=(table, k, count, score))
+
+    def ring_insert():  # the trainer's own insert; last: it moves rb's rings on
+        rb.add_batch(obs, act, obs, rew, done, strata)
     for name, f in (("update + sample (one launch)", upd_sample), ("update alone", upd), ("sample + gather", smp),
-                    ("ref insert + mask advance", ref_insert)):
+                    ("ref insert + mask advance", ref_insert), ("ring insert (rank + copy)", ring_insert)):
         print(f"{name:32s} {timed(f):8.2f} us", flush=True)
 
 
