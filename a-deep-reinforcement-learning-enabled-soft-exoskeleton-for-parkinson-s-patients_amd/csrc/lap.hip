@@ -259,8 +259,13 @@ __device__ __forceinline__ float sel4(int r, float a, float b, float c, float d)
 }
 
 // The descent from `node` at level lv to a leaf: at every level go left when
-// val <= left (or the right subtree is empty), else subtract left and go
-// right.  The children of the next (up to) three levels are read together --
+// val <= left and the left subtree is not empty (or the right one is), else
+// subtract left and go right.  The `left > 0` term matters only for val == 0
+// over an empty left subtree: a buffer's own tree has none left of a filled
+// slot (the same leaf as without the term), a view's tree (lap_view_build)
+// has them wherever the leading rows are foreign, and the walk must not end
+// on a zero leaf there.  The LDS levels of lap_update_sample apply the same
+// rule.  The children of the next (up to) three levels are read together --
 // 2 + 4 + 8 nodes at 2n, 4n, 8n -- and the three choices made from registers:
 // the same comparisons and subtractions as the one-level walk, a third of its
 // dependent memory round trips.  Returns the leaf node.
@@ -278,7 +283,7 @@ __device__ __forceinline__ int descend_from(At at, float val, int node, int lv, 
             c4 = at(n3 + 4), c5 = at(n3 + 5), c6 = at(n3 + 6), c7 = at(n3 + 7);
         }
         int r;
-        if (val <= a0 || a1 <= 0.0f) {
+        if ((val <= a0 && a0 > 0.0f) || a1 <= 0.0f) {
             r = 0;
         } else {
             val -= a0;
@@ -286,7 +291,7 @@ __device__ __forceinline__ int descend_from(At at, float val, int node, int lv, 
         }
         if (k >= 2) {
             const float l = r ? b2 : b0, rt = r ? b3 : b1;
-            if (val <= l || rt <= 0.0f) {
+            if ((val <= l && l > 0.0f) || rt <= 0.0f) {
                 r = 2 * r;
             } else {
                 val -= l;
@@ -294,7 +299,7 @@ __device__ __forceinline__ int descend_from(At at, float val, int node, int lv, 
             }
             if (k >= 3) {
                 const float l3 = sel4(r, c0, c2, c4, c6), r3 = sel4(r, c1, c3, c5, c7);
-                if (val <= l3 || r3 <= 0.0f) {
+                if ((val <= l3 && l3 > 0.0f) || r3 <= 0.0f) {
                     r = 2 * r;
                 } else {
                     val -= l3;
@@ -1265,7 +1270,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_kernel(float *t
         int node = 1, lv = 0;
         for (; lv < levels && 2 * node + 1 < lim; ++lv) {
             const float left = top[2 * node], right = top[2 * node + 1];
-            if (val <= left || right <= 0.0f) {
+            if ((val <= left && left > 0.0f) || right <= 0.0f) {
                 node = 2 * node;
             } else {
                 val -= left;
@@ -1491,7 +1496,7 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_chain_kernel(
         int node = 1;
         for (int lv = 0; lv < ltop; ++lv) {
             const float left = top[2 * node], right = top[2 * node + 1];
-            if (val <= left || right <= 0.0f) {
+            if ((val <= left && left > 0.0f) || right <= 0.0f) {
                 node = 2 * node;
             } else {
                 val -= left;
@@ -1511,6 +1516,158 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_update_sample_chain_kernel(
     }
     // ---- trip 5; `call` was read (and used) before this add: no fence needed
     if (t == 0) rng_ticket(rng, call);
+}
+
+// ---------------------------------------------------------------- behaviour-policy column, views
+// source[n_strata][capacity + 1] (int32, -1 = untagged) names the behaviour
+// policy of every stored row; it is laid out like reward / not_done, so the
+// storage row index r = s (capacity + 1) + slot addresses it.
+
+// lap_store_copy_kernel that also writes the row's source (src == nullptr: -1).
+// Inactive rows land in the trash row `capacity`, rows without a stratum
+// (row_of < 0) write nothing.
+__global__ __launch_bounds__(256) void lap_store_copy_src_kernel(lap_storage_desc st, Rows in, int n,
+                                                                 const int32_t *row_of, const int32_t *src,
+                                                                 int32_t *source) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= n) return;
+    const long r = row_of[i];
+    if (r < 0) return;
+    store_row_wave(st, in, r, i, lane);
+    if (lane == 0) source[r] = src ? src[i] : -1;
+}
+
+// Rows per source id of every stratum, slots < size[s] only: out[s][id] for
+// 0 <= id < K, out[s][K] the untagged rows (ids >= K are not counted).  The
+// workgroups of a stratum (blockIdx.x) each count COUNT_SLOTS slots in an LDS
+// histogram and add their non-zero bins to `out` (zeroed by the launcher).
+// A thread loads COUNT_U slots before it counts any of them: one slot per
+// round trip left the launch waiting for memory 64 times in a row.
+constexpr int COUNT_THREADS = 256;
+constexpr int COUNT_MAXK = 4096;
+constexpr int COUNT_SLOTS = 16384;  // slots per workgroup
+constexpr int COUNT_U = 8;          // loads in flight per thread
+__global__ __launch_bounds__(COUNT_THREADS) void lap_source_counts_kernel(const int32_t *source, int capacity,
+                                                                          const int32_t *size, int K,
+                                                                          unsigned long long *out) {
+    __shared__ int hist[COUNT_MAXK + 1];
+    const int s = blockIdx.y, t = threadIdx.x;
+    const int sz = min(size[s], capacity);
+    const int32_t *col = source + (size_t)s * (capacity + 1);
+    for (int k = t; k <= K; k += COUNT_THREADS) hist[k] = 0;
+    __syncthreads();
+    const int lo = blockIdx.x * COUNT_SLOTS, hi = min(sz, lo + COUNT_SLOTS);
+    for (int i0 = lo + t; i0 < hi; i0 += COUNT_U * COUNT_THREADS) {
+        int v[COUNT_U];
+#pragma unroll
+        for (int u = 0; u < COUNT_U; ++u) {
+            const int i = i0 + u * COUNT_THREADS;
+            v[u] = i < hi ? col[i] : K;  // K: not counted
+        }
+#pragma unroll
+        for (int u = 0; u < COUNT_U; ++u)
+            if (v[u] < K) atomicAdd(&hist[v[u] < 0 ? K : v[u]], 1);
+    }
+    __syncthreads();
+    for (int k = t; k <= K; k += COUNT_THREADS)
+        if (hist[k]) atomicAdd(&out[(size_t)s * (K + 1) + k], (unsigned long long)hist[k]);
+}
+
+// lap_view_build: the trees of a view over the same rows.  Leaf i of stratum
+// s is base leaf i (inherit) or 1 when i < size[s], source >= 0 and
+// keep[source], else 0; every internal node is T[2n] + T[2n + 1] of its final
+// children -- the sums propagate / propagate_span compute, so a view that
+// keeps every row and inherits is the base's tree bit for bit.
+// Pass 1 (grid: leaf blocks x strata): a workgroup owns VIEW_LEAVES
+// consecutive leaves (the whole stratum when cap is smaller): the kept mask
+// from coalesced source loads into LDS, the leaves as float4 stores, then the
+// block's own subtree level by level in LDS -- local node n at depth d (w =
+// 2^d nodes) is node root * w + (n - w) of the tree.  With inherit the block's
+// largest kept leaf goes to max_priority (zeroed by the launcher) with one
+// atomic; without, max_priority = 1.
+// Pass 2 (one workgroup per stratum, only when cap > VIEW_LEAVES, a later
+// launch): the cap / VIEW_LEAVES subtree roots pass 1 wrote, reduced to node
+// 1 in LDS.  No workgroup reads what another wrote in the same launch.
+constexpr int VIEW_LEAVES = 4096;
+constexpr int VIEW_THREADS = 512;
+static_assert((1 << MAXLV) / VIEW_LEAVES <= VIEW_LEAVES, "pass 2 holds the subtree roots in 2 VIEW_LEAVES floats");
+__global__ __launch_bounds__(VIEW_THREADS) void lap_view_leaves_kernel(float *tree, float *maxp, const float *base,
+                                                                       int cap, int capacity, const int32_t *size,
+                                                                       const int32_t *source, const uint8_t *keep,
+                                                                       int n_keep, bool inherit) {
+    __shared__ __attribute__((aligned(16))) float lt[2 * VIEW_LEAVES];
+    __shared__ float red[VIEW_THREADS / 64];
+    const int s = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
+    const int nl = min(VIEW_LEAVES, cap);  // this block's leaves [i0, i0 + nl)
+    const int i0 = b * nl, root = cap / nl + b;
+    float *T = stratum_tree(tree, s, cap);
+    const float *B = base + (size_t)s * 2 * cap + cap;
+    const int sz = min(size[s], capacity);
+    const int32_t *col = source + (size_t)s * (capacity + 1);
+    for (int j = t; j < nl; j += VIEW_THREADS) {
+        const int i = i0 + j;
+        const int v = i < sz ? col[i] : -1;
+        lt[nl + j] = (v >= 0 && v < n_keep && keep[v]) ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    float mx = 0.0f;
+    if ((nl & 3) == 0) {
+        for (int q = t; q < nl / 4; q += VIEW_THREADS) {
+            float4 v = *reinterpret_cast<const float4 *>(&lt[nl + 4 * q]);
+            if (inherit) {
+                const float4 p = ld4(B + i0 + 4 * q);
+                v.x = v.x != 0.0f ? p.x : 0.0f;
+                v.y = v.y != 0.0f ? p.y : 0.0f;
+                v.z = v.z != 0.0f ? p.z : 0.0f;
+                v.w = v.w != 0.0f ? p.w : 0.0f;
+                *reinterpret_cast<float4 *>(&lt[nl + 4 * q]) = v;
+                mx = fmaxf(fmaxf(mx, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+            }
+            st4(T + cap + i0 + 4 * q, v);
+        }
+    } else {  // cap 1 or 2
+        for (int j = t; j < nl; j += VIEW_THREADS) {
+            float v = lt[nl + j];
+            if (inherit) {
+                v = v != 0.0f ? B[i0 + j] : 0.0f;
+                lt[nl + j] = v;
+                mx = fmaxf(mx, v);
+            }
+            T[cap + i0 + j] = v;
+        }
+    }
+    for (int w = nl / 2; w >= 1; w >>= 1) {
+        __syncthreads();
+        for (int j = t; j < w; j += VIEW_THREADS) {
+            const int n = w + j;
+            const float v = lt[2 * n] + lt[2 * n + 1];
+            lt[n] = v;
+            T[(size_t)root * w + j] = v;
+        }
+    }
+    if (inherit) {
+        mx = wave_max_to(red, mx);
+        __syncthreads();
+        block_max_to(maxp, mx, red);  // leaves >= 0: int order == float order
+    } else if (s == 0 && b == 0 && t == 0) {
+        *maxp = 1.0f;
+    }
+}
+
+__global__ __launch_bounds__(UPD_THREADS) void lap_view_top_kernel(float *tree, int cap) {
+    __shared__ float top[2 * VIEW_LEAVES];
+    float *T = stratum_tree(tree, blockIdx.x, cap);
+    const int nb = cap / VIEW_LEAVES, t = threadIdx.x;  // the subtree roots are nodes [nb, 2 nb)
+    for (int j = t; j < nb; j += UPD_THREADS) top[nb + j] = T[nb + j];
+    for (int w = nb / 2; w >= 1; w >>= 1) {
+        __syncthreads();
+        for (int j = t; j < w; j += UPD_THREADS) {
+            const int n = w + j;
+            const float v = top[2 * n] + top[2 * n + 1];
+            top[n] = v;
+            T[n] = v;
+        }
+    }
 }
 
 int rc(hipError_t e) { return e == hipSuccess ? EXO_OK : EXO_EDEVICE; }
@@ -1642,12 +1799,9 @@ int lap_totals(const lap_tree_desc *t, float *out, void *stream) {
     return rc(hipGetLastError());
 }
 
-int lap_store_batch(const lap_tree_desc *t, const lap_storage_desc *st, const float *state, const float *action,
-                    const float *next_state, const float *reward, const uint8_t *done, const int32_t *strata,
-                    const uint8_t *active, float action_scale, int32_t n, int32_t *row_ws, void *stream) {
-    const Rows in{state, action, next_state, reward, done, action_scale};
-    if (!store_args_ok(t, st, in, strata, n) || !st->ptr || !row_ws) return EXO_EINVAL;
-    if (n == 0) return EXO_OK;
+// lap_store_batch's first launch: the slots, leaves, span and ring state
+static int launch_store_rank(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *strata,
+                             const uint8_t *active, int32_t n, int32_t *row_ws, void *stream) {
     if (n > 4 * STORE_CHUNK)
         hipLaunchKernelGGL(lap_store_rank_kernel<16>, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, st->ptr, st->size, strata,
@@ -1656,7 +1810,60 @@ int lap_store_batch(const lap_tree_desc *t, const lap_storage_desc *st, const fl
         hipLaunchKernelGGL(lap_store_rank_kernel<4>, dim3(t->n_strata), dim3(UPD_THREADS), 0, (hipStream_t)stream,
                            t->tree, t->max_priority, t->cap, levels_of(t), t->capacity, st->ptr, st->size, strata,
                            active, n, row_ws);
+    return rc(hipGetLastError());
+}
+
+int lap_store_batch_src(const lap_tree_desc *t, const lap_storage_desc *st, const float *state, const float *action,
+                        const float *next_state, const float *reward, const uint8_t *done, const int32_t *strata,
+                        const uint8_t *active, float action_scale, int32_t n, int32_t *row_ws, const int32_t *src,
+                        int32_t *source, void *stream) {
+    const Rows in{state, action, next_state, reward, done, action_scale};
+    if (!store_args_ok(t, st, in, strata, n) || !st->ptr || !row_ws || !source) return EXO_EINVAL;
+    if (n == 0) return EXO_OK;
+    if (launch_store_rank(t, st, strata, active, n, row_ws, stream) != EXO_OK) return EXO_EDEVICE;
+    hipLaunchKernelGGL(lap_store_copy_src_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, in, n,
+                       row_ws, src, source);
+    return rc(hipGetLastError());
+}
+
+int lap_source_counts(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *source, int32_t n_sources,
+                      int64_t *out, void *stream) {
+    if (!valid(t) || !st || !st->size || !source || !out || n_sources < 0 || n_sources > COUNT_MAXK)
+        return EXO_EINVAL;
+    hipError_t e = hipMemsetAsync(out, 0, (size_t)t->n_strata * (n_sources + 1) * sizeof(int64_t),
+                                  (hipStream_t)stream);
+    if (e != hipSuccess) return EXO_EDEVICE;
+    hipLaunchKernelGGL(lap_source_counts_kernel, dim3((t->capacity + COUNT_SLOTS - 1) / COUNT_SLOTS, t->n_strata),
+                       dim3(COUNT_THREADS), 0, (hipStream_t)stream, source, t->capacity, st->size, n_sources,
+                       (unsigned long long *)out);
+    return rc(hipGetLastError());
+}
+
+int lap_view_build(const lap_tree_desc *view, const lap_tree_desc *base, const lap_storage_desc *st,
+                   const int32_t *source, const uint8_t *keep, int32_t n_keep, int32_t inherit, void *stream) {
+    if (!valid(view) || !valid(base) || view->tree == base->tree || view->max_priority == base->max_priority ||
+        view->n_strata != base->n_strata || view->capacity != base->capacity || view->cap != base->cap || !st ||
+        !st->size || !source || !keep || n_keep <= 0)
+        return EXO_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (inherit && hipMemsetAsync(view->max_priority, 0, sizeof(float), s) != hipSuccess) return EXO_EDEVICE;
+    const int cap = view->cap, nl = std::min(VIEW_LEAVES, cap);
+    hipLaunchKernelGGL(lap_view_leaves_kernel, dim3(cap / nl, view->n_strata), dim3(VIEW_THREADS), 0, s, view->tree,
+                       view->max_priority, base->tree, cap, view->capacity, st->size, source, keep, n_keep,
+                       inherit != 0);
     if (hipGetLastError() != hipSuccess) return EXO_EDEVICE;
+    if (cap > VIEW_LEAVES)
+        hipLaunchKernelGGL(lap_view_top_kernel, dim3(view->n_strata), dim3(UPD_THREADS), 0, s, view->tree, cap);
+    return rc(hipGetLastError());
+}
+
+int lap_store_batch(const lap_tree_desc *t, const lap_storage_desc *st, const float *state, const float *action,
+                    const float *next_state, const float *reward, const uint8_t *done, const int32_t *strata,
+                    const uint8_t *active, float action_scale, int32_t n, int32_t *row_ws, void *stream) {
+    const Rows in{state, action, next_state, reward, done, action_scale};
+    if (!store_args_ok(t, st, in, strata, n) || !st->ptr || !row_ws) return EXO_EINVAL;
+    if (n == 0) return EXO_OK;
+    if (launch_store_rank(t, st, strata, active, n, row_ws, stream) != EXO_OK) return EXO_EDEVICE;
     hipLaunchKernelGGL(lap_store_copy_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *st, in, n,
                        row_ws);
     return rc(hipGetLastError());

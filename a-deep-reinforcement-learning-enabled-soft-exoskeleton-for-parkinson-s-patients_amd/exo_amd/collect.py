@@ -61,11 +61,17 @@ class Collector:
 
     graph=True replays the step from graphs captured on a single stream, one
     per observation-buffer parity (graphs.new_graph / graphs.capture; no forks,
-    no side streams); release() destroys them through graphs.release_graphs."""
+    no side streams); release() destroys them through graphs.release_graphs.
+
+    tag_sources=True: the replay records which policy produced every row
+    (replay.enable_sources(); add_batch(source=...) with env i's policy, an
+    int32 device tensor built once from seg) -- the same launches per step --
+    so replay.view([p]) is policy p's dataset and replay.source_counts(K) its
+    size per stratum."""
 
     def __init__(self, policy_set, envs_per_policy, replay, sigma=0.1, sigma_dec=0.0, clip=0.0, env_kwargs=None,
                  per_policy_env_kwargs=None, seed=0, physics="ideal", max_action=1.0, strata=None, graph=False,
-                 noise="gaussian", beta=1.0):
+                 noise="gaussian", beta=1.0, tag_sources=False):
         from .fused import MultiNoise, PinkNoise, per_policy
         from .vec_env import VecExoskeletonEnv
         K = len(policy_set)
@@ -104,6 +110,10 @@ class Collector:
         else:
             self.noise = MultiNoise(policy_set, sig, dec, clip)
         self.strata = torch.as_tensor(strata_h, device=d)
+        self.sources = None
+        if tag_sources:
+            replay.enable_sources()
+            self.sources = torch.as_tensor(np.repeat(np.arange(K, dtype=np.int32), self.counts), device=d)
         # two observation buffers used in alternation (VecTrainer): step c reads
         # obs[c], the env writes the next observation into obs[1 - c]
         o0 = self.env.reset()
@@ -162,7 +172,7 @@ class Collector:
         act = self._select(obs)
         nobs, rew, done, _ = self.env.step(act, active=self.active, out=out, with_info=False)
         # before the in-place resets: next_state of a done row is the terminal observation
-        self.replay.add_batch(obs, act, nobs, rew, done, self.strata, self.active)
+        self.replay.add_batch(obs, act, nobs, rew, done, self.strata, self.active, source=self.sources)
         self._ret32.add_(rew)
         self._ret64.add_(rew)
         self._d64.copy_(done)

@@ -87,6 +87,7 @@ class LAP:
         self._batch = (sn[0], torch.empty((B, action_dim), **f32), sn[1], torch.empty((B, 1), **f32),
                        torch.empty((B, 1), **f32))
         self._row_ws = None
+        self.source = None  # the behaviour-policy column (enable_sources)
         self._init_tree()
 
     def _stream(self):
@@ -112,6 +113,7 @@ class LAP:
     # ---------------------------------------------------------------- adds
     def add(self, state, action, next_state, reward, done, tremor_num):
         """Agent/TD7_buffer_multi_agent.py:49-63."""
+        self._no_sources("add")
         s, p = int(tremor_num), self.ptr
         dev = self.device
         self.state[s, p] = torch.as_tensor(np.asarray(state, dtype=np.float32), device=dev)
@@ -151,21 +153,68 @@ class LAP:
         act = None if active is None else u8(active).contiguous()
         return st, ac, nx, rw, dn, sr, act
 
-    def add_batch(self, state, action, next_state, reward, done, strata, active=None):
+    # ------------------------------------------- the behaviour-policy column
+    def enable_sources(self):
+        """Allocate self.source, int32 [E, max_size + 1] filled with -1: the
+        behaviour policy of every stored row (-1 = untagged), written by
+        add_batch(source=...).  Call it eagerly, before any graph capture;
+        idempotent.  Rows already stored stay untagged."""
+        if self.source is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("LAP.enable_sources: run once eagerly before graph capture")
+            self.source = torch.full((self.num_envs, self.max_size + 1), -1, dtype=torch.int32, device=self.device)
+        return self.source
+
+    def _no_sources(self, what):
+        if self.source is not None:
+            raise ValueError(f"LAP.{what}: not on a buffer with a source column (add_batch / load_dataset only)")
+
+    def source_counts(self, K):
+        """Stored rows per source id and stratum: int64 [E, K + 1] on the
+        device, column K the untagged rows (lap_source_counts, one kernel; ids
+        >= K are not counted)."""
+        if self.source is None:
+            raise ValueError("LAP.source_counts: no source column (enable_sources)")
+        out = torch.empty((self.num_envs, int(K) + 1), dtype=torch.int64, device=self.device)
+        nat.check(nat.lib().lap_source_counts(ctypes.byref(self._desc), ctypes.byref(self._store),
+                                              nat.ptr(self.source), int(K), nat.ptr(out), self._stream()),
+                  "lap_source_counts")
+        return out
+
+    def view(self, keep, inherit=False, batch_size=None):
+        """A LapView of the rows whose source is in `keep` (see LapView)."""
+        return LapView(self, keep, inherit=inherit, batch_size=batch_size)
+
+    def add_batch(self, state, action, next_state, reward, done, strata, active=None, source=None):
         """One vectorised env step: row i goes to stratum strata[i] (int32 [N]) if
         active[i] (bool/uint8 [N], default all) -- lap_store_batch, two kernels,
-        no host synchronisation."""
+        no host synchronisation.  source (int32 [N] on the device, values >= 0):
+        the behaviour policy of every row, into self.source by the row-copy
+        launch (lap_store_batch_src, the same two kernels; the column is
+        enabled if needed); without it a buffer that has the column records -1."""
         n = state.shape[0]
         if self._row_ws is None or self._row_ws.numel() < n:
             self._row_ws = torch.empty((n,), dtype=torch.int32, device=self.device)
         st, ac, nx, rw, dn, sr, act = self._step_args(state, action, next_state, reward, done, strata, active)
+        if source is not None or self.source is not None:
+            self.enable_sources()
+            if source is not None:
+                if source.dtype != torch.int32 or source.device != self.device or source.numel() != n:
+                    raise ValueError(f"add_batch: source must be int32 [{n}] on {self.device}")
+                source = source.reshape(n).contiguous()
+            nat.check(nat.lib().lap_store_batch_src(ctypes.byref(self._desc), ctypes.byref(self._store), nat.ptr(st),
+                                                    nat.ptr(ac), nat.ptr(nx), nat.ptr(rw), nat.ptr(dn), nat.ptr(sr),
+                                                    nat.ptr(act), float(self.normalize_actions), n,
+                                                    nat.ptr(self._row_ws), nat.ptr(source), nat.ptr(self.source),
+                                                    self._stream()), "lap_store_batch_src")
+            return
         nat.check(nat.lib().lap_store_batch(ctypes.byref(self._desc), ctypes.byref(self._store), nat.ptr(st),
                                             nat.ptr(ac), nat.ptr(nx), nat.ptr(rw), nat.ptr(dn), nat.ptr(sr),
                                             nat.ptr(act), float(self.normalize_actions), n, nat.ptr(self._row_ws),
                                             self._stream()), "lap_store_batch")
 
     # ------------------------------------------------------ datasets (offline)
-    def load_dataset(self, state, action, next_state, reward, done, strata, chunk=65536):
+    def load_dataset(self, state, action, next_state, reward, done, strata, chunk=65536, source=None):
         """A dataset of transitions (numpy or torch, host or device; row i to
         stratum strata[i]) through add_batch in row order: ring semantics per
         stratum (a stratum given more rows than max_size keeps the newest),
@@ -173,7 +222,9 @@ class LAP:
         hold at most `chunk` rows and at most max_size rows of one stratum
         (one add_batch call must not wrap a ring onto itself).  ValueError if
         a stratum is empty afterwards: sample() draws batch_size rows from
-        every stratum.  One host read of the ring sizes at the end."""
+        every stratum.  One host read of the ring sizes at the end.  source
+        (int [n], values >= 0; export_dataset's key of a buffer with the
+        column): the rows' behaviour policies, into self.source."""
         cpu = lambda t: torch.as_tensor(t)  # noqa: E731
         sr = cpu(strata).to(torch.int64).reshape(-1).cpu()
         n = sr.numel()
@@ -182,9 +233,12 @@ class LAP:
         cols = [cpu(state).reshape(n, self.state_dim), cpu(action).reshape(n, self.action_dim),
                 cpu(next_state).reshape(n, self.state_dim), cpu(reward).reshape(n), cpu(done).reshape(n)]
         cols[4] = cols[4].to(torch.uint8) if cols[4].dtype != torch.bool else cols[4]
+        if source is not None:
+            source = cpu(source).reshape(n).to(torch.int32)
         for lo, hi in self._dataset_chunks(sr, int(chunk)):
             s, a, s2, r, d = (c[lo:hi].to(self.device) for c in cols)
-            self.add_batch(s, a, s2, r, d, sr[lo:hi].to(device=self.device, dtype=torch.int32))
+            self.add_batch(s, a, s2, r, d, sr[lo:hi].to(device=self.device, dtype=torch.int32),
+                           source=None if source is None else source[lo:hi].to(self.device))
         empty = (self.size_s == 0).nonzero().reshape(-1).tolist()
         if empty:
             raise ValueError(f"load_dataset: no rows for strata {empty} (every stratum is sampled)")
@@ -214,8 +268,9 @@ class LAP:
     def export_dataset(self):
         """The rows the per-stratum rings hold, oldest first per stratum (after
         a wrap too), as CPU tensors: state, action (de-normalised), next_state,
-        reward [n], done [n] (uint8), strata [n] (int32).  load_dataset(**it)
-        into a fresh buffer of the same capacity holds the same rows."""
+        reward [n], done [n] (uint8), strata [n] (int32), and source [n] (int32)
+        when the buffer has the column.  load_dataset(**it) into a fresh
+        buffer of the same capacity holds the same rows."""
         C = self.max_size
         size, ptr = self.size_s.cpu().tolist(), self.ptr_s.cpu().tolist()
         rows, strata = [], []
@@ -225,9 +280,12 @@ class LAP:
             strata.append(torch.full((size[s],), s, dtype=torch.int32))
         rows = torch.cat(rows).to(self.device)
         take = lambda t: t.reshape(-1, t.shape[-1]).index_select(0, rows).cpu()  # noqa: E731
-        return dict(state=take(self.state), action=take(self.action) * self.normalize_actions,
-                    next_state=take(self.next_state), reward=take(self.reward).reshape(-1),
-                    done=(1.0 - take(self.not_done).reshape(-1)).to(torch.uint8), strata=torch.cat(strata))
+        out = dict(state=take(self.state), action=take(self.action) * self.normalize_actions,
+                   next_state=take(self.next_state), reward=take(self.reward).reshape(-1),
+                   done=(1.0 - take(self.not_done).reshape(-1)).to(torch.uint8), strata=torch.cat(strata))
+        if self.source is not None:  # int32 [n], -1 = untagged
+            out["source"] = self.source.reshape(-1).index_select(0, rows).cpu()
+        return out
 
     def add_batch_ref(self, state, action, next_state, reward, done, strata, active=None, advance=None):
         """LAP.add (:49-63) for every active row in row order -- the training
@@ -239,6 +297,7 @@ class LAP:
         host synchronisation.  advance = (table, k, count, score): the
         trainer's mask advance in the same launch (lap_store_batch_ref_fused_adv;
         `active` is then advanced in place, the rewards added into score)."""
+        self._no_sources("add_batch_ref")
         n = state.shape[0]
         if self._ref_ws is None or self._ref_ws.numel() < 3 * n:
             # zeroed: its first word is the fused launch's ticket (left zero)
@@ -271,6 +330,7 @@ class LAP:
     def ref_plan(self, table, strata, offs, total, plan):
         """plan[k][e] (int32 [rows][n]) for the mask table rows (uint8/bool
         [rows][n]); offs: int64 device [rows], the adds before each row."""
+        self._no_sources("ref_plan")
         rows, n = table.shape
         if getattr(self, "_ref_add_ws", None) is None or self._ref_add_ws.numel() < max(int(total), 1):
             self._ref_add_ws = torch.empty((max(int(total), 1),), dtype=torch.int32, device=self.device)
@@ -284,6 +344,7 @@ class LAP:
                  k_dev=None, count=None, counts_table=None, score=None):
         """One step of a planned round (see ref_plan): the transitions to their
         planned slots, score += reward where active, the next mask in place."""
+        self._no_sources("ref_step")
         rows, n = plan.shape
         tb = table.view(torch.uint8) if table.dtype == torch.bool else table
         dn = done.view(torch.uint8) if done.dtype == torch.bool else done.to(torch.uint8)
@@ -297,6 +358,7 @@ class LAP:
 
     def ref_commit(self, plan, strata, total):
         """The end of a planned round: leaves, the round's span, the pointer."""
+        self._no_sources("ref_commit")
         rows, n = plan.shape
         nat.check(nat.lib().lap_ref_commit(ctypes.byref(self._desc), ctypes.byref(self._store),
                                            nat.ptr(self.ref_state), nat.ptr(plan), rows, n, nat.ptr(strata),
@@ -426,4 +488,81 @@ class LAP:
         self.ptr_s.zero_()
         self.size_s.zero_()
         self.ref_state.zero_()
+        if self.source is not None:
+            self.source.fill_(-1)
         self._init_tree()
+
+
+class LapView(LAP):
+    """LAP.view(keep, inherit=False, batch_size=None): the rows of `base`
+    whose source id is in `keep`, as a replay of their own for the learner
+    (Agent.use_replay, OfflineTrainer).  The view shares the base's row
+    tensors, source column and ring state (ptr_s / size_s) -- no row is copied
+    -- and owns a second set of sum trees (lap_view_build: the leaf of a
+    foreign or untagged row is 0, so no descent reaches it), its max_priority,
+    DeviceRNG stream, batch slots and ind.  sample, sample_indices,
+    update_priority, update_priority_and_sample(_td), reset_max_priority,
+    priority, max_priority and totals are LAP's, on the view's trees; the
+    base's priorities are neither read (inherit=False: every kept row starts at
+    priority 1, max_priority 1; inherit=True: at the base's leaf, max_priority
+    their maximum) nor written afterwards.
+
+    A view is a snapshot of the base at view() / rebuild(): rows inserted into
+    the base afterwards are not in it (a wrapped ring may even overwrite a kept
+    row with a foreign one), and inserts do not update live views.  rebuild()
+    runs the build again from the base as it is then, which also discards the
+    view's learned priorities.  ValueError if a stratum keeps no row (one host
+    read of source_counts): sample() draws from every stratum.  Inserts,
+    reset_buffer and load_dataset raise on a view."""
+
+    def __init__(self, base, keep, inherit=False, batch_size=None):
+        if isinstance(base, LapView):
+            raise ValueError("LAP.view: take the view from the base buffer")
+        if base.source is None:
+            raise ValueError("LAP.view: the buffer has no source column (enable_sources / add_batch(source=...))")
+        keep = sorted({int(k) for k in keep})
+        if not keep or keep[0] < 0:
+            raise ValueError("LAP.view: keep must list source ids >= 0")
+        self.base, self.keep, self.inherit = base, keep, bool(inherit)
+        for name in ("device", "max_size", "max_action", "num_envs", "state_dim", "action_dim", "normalize_actions",
+                     "prioritized", "state", "action", "next_state", "reward", "not_done", "ptr_s", "size_s", "source",
+                     "_store", "_cap", "device_rng"):
+            setattr(self, name, getattr(base, name))
+        self.batch_size = int(batch_size if batch_size is not None else base.batch_size)
+        E, C, cap = self.num_envs, self.max_size, self._cap
+        f32 = dict(device=self.device, dtype=torch.float32)
+        i32 = dict(device=self.device, dtype=torch.int32)
+        self._tree = torch.zeros((E, 2 * cap), **f32)
+        self._maxp = torch.ones((1,), **f32)
+        self._desc = nat.LapTreeDesc(self._tree.data_ptr(), self._maxp.data_ptr(), E, C, cap)
+        table = torch.zeros(keep[-1] + 1, dtype=torch.uint8)
+        table[keep] = 1
+        self._keep = table.to(self.device)
+        self.ind = None
+        self._u = torch.empty((E, self.batch_size), **f32)
+        from .ops import DeviceRNG
+        self._rng = DeviceRNG(self.device, 3)
+        self._idx = torch.empty((E, self.batch_size), **i32)
+        B = E * self.batch_size
+        sn = torch.empty((2, B, self.state_dim), **f32)
+        self._batch = (sn[0], torch.empty((B, self.action_dim), **f32), sn[1], torch.empty((B, 1), **f32),
+                       torch.empty((B, 1), **f32))
+        self.rebuild()
+
+    def rebuild(self):
+        """Build the view's trees again from the base as it is now."""
+        counts = self.base.source_counts(self._keep.numel())[:, :-1].cpu()
+        empty = (counts[:, self.keep].sum(1) == 0).nonzero().reshape(-1).tolist()
+        if empty:
+            raise ValueError(f"LAP.view: no rows of sources {self.keep} in strata {empty} (every stratum is sampled)")
+        nat.check(nat.lib().lap_view_build(ctypes.byref(self._desc), ctypes.byref(self.base._desc),
+                                           ctypes.byref(self._store), nat.ptr(self.source), nat.ptr(self._keep),
+                                           self._keep.numel(), int(self.inherit), self._stream()), "lap_view_build")
+        return self
+
+    def _not_on_a_view(self, *a, **k):
+        raise ValueError("LapView: a view is read-only storage (insert into, reset or load the base buffer, "
+                         "then rebuild())")
+
+    add = add_batch = add_batch_ref = ref_plan = ref_step = ref_commit = _not_on_a_view
+    load_dataset = reset_buffer = enable_sources = view = _not_on_a_view

@@ -1540,8 +1540,27 @@ class Agent:
 
     def load_dataset(self, path, chunk=65536):
         """A save_dataset file (a dict of tensors: state, action, next_state,
-        reward, done, strata) into the replay (LAP.load_dataset)."""
+        reward, done, strata, and source when the rows were tagged) into the
+        replay (LAP.load_dataset)."""
         self.replay_buffer.load_dataset(**torch.load(path, weights_only=True), chunk=chunk)
+
+    def use_replay(self, replay):
+        """Train from `replay` (a LAP or a LAP.view of one, e.g. one behaviour
+        policy's rows of a collected buffer) instead of the agent's own buffer:
+        it becomes self.replay_buffer.  With Agent(..., offline=True,
+        buffer_size=1) the agent need not own a large buffer.  The replay must
+        match the agent's dimensions, strata, batch size and device.  One GPU
+        only: nothing is folded per rank."""
+        if self.sync.world > 1:
+            raise ValueError("Agent.use_replay: one GPU only (a shared replay is not sharded over ranks)")
+        rb = self.replay_buffer
+        want = (rb.state_dim, rb.action_dim, rb.num_envs, rb.batch_size, rb.device)
+        got = (replay.state_dim, replay.action_dim, replay.num_envs, replay.batch_size, replay.device)
+        if want != got:
+            raise ValueError(f"Agent.use_replay: the replay's (state_dim, action_dim, num_envs, batch_size, device) "
+                             f"{got} are not the agent's {want}")
+        self.replay_buffer = replay
+        return replay
 
     def maybe_train_and_checkpoint(self, ep_timesteps, ep_return, train=None):
         """:296-312 (the episode return is MIN-reduced over data-parallel ranks).

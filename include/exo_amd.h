@@ -349,6 +349,39 @@ int lap_store_batch(const lap_tree_desc *t, const lap_storage_desc *st, const fl
                     const uint8_t *done_dev, const int32_t *strata_dev, const uint8_t *active_dev, float action_scale,
                     int32_t n, int32_t *row_ws_dev, void *stream);
 
+/* lap_store_batch that also records which behaviour policy produced each row:
+ * source_dev[n_strata][capacity + 1] (int32, caller-owned, -1 = untagged) is a
+ * column laid out like reward / not_done, and the row-copy launch writes
+ * src_dev[i] (int32 [n], values >= 0; NULL: -1) to the slot of row i -- the
+ * same two launches as lap_store_batch, the same rows, leaves and ring state.
+ * Inactive rows write the trash slot `capacity`, rows whose stratum is out of
+ * range write nothing. */
+int lap_store_batch_src(const lap_tree_desc *t, const lap_storage_desc *st, const float *state_dev,
+                        const float *action_dev, const float *next_state_dev, const float *reward_dev,
+                        const uint8_t *done_dev, const int32_t *strata_dev, const uint8_t *active_dev,
+                        float action_scale, int32_t n, int32_t *row_ws_dev, const int32_t *src_dev,
+                        int32_t *source_dev, void *stream);
+
+/* Rows per source of every stratum, over the slots < size[s]:
+ * out_dev[n_strata][n_sources + 1] (int64), column id for 0 <= id < n_sources
+ * (<= 4096), column n_sources the untagged rows (-1); larger ids are not
+ * counted.  One kernel (LDS histograms) after a memset of out_dev. */
+int lap_source_counts(const lap_tree_desc *t, const lap_storage_desc *st, const int32_t *source_dev,
+                      int32_t n_sources, int64_t *out_dev, void *stream);
+
+/* The trees of a view: a second lap_tree_desc (its own tree and max_priority,
+ * the base's n_strata / capacity / cap) over the base's rows.  Leaf i of
+ * stratum s = (inherit ? base leaf i : 1) when i < size[s], source >= 0 and
+ * keep_dev[source] (uint8 [n_keep]; ids >= n_keep are not kept), else 0; every
+ * internal node = T[2n] + T[2n+1] in fp32 -- the sums lap_update / the inserts
+ * compute, so every sampling and update entry above works on the view's desc
+ * with the base's lap_storage_desc.  max_priority = 1, or with inherit the
+ * largest kept leaf.  One launch over blocks of 4,096 leaves, and a second
+ * (one workgroup per stratum) for the levels above them when cap > 4,096. */
+int lap_view_build(const lap_tree_desc *view, const lap_tree_desc *base, const lap_storage_desc *st,
+                   const int32_t *source_dev, const uint8_t *keep_dev, int32_t n_keep, int32_t inherit,
+                   void *stream);
+
 /* LAP.add (Agent/TD7_buffer_multi_agent.py:49-63) called once per active env
  * of one vectorised step, in env order -- the training script's per-env loop
  * (Simulation/Exoskeleton_agent_train.py:139-142) -- with the reference's

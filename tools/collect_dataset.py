@@ -23,10 +23,16 @@ times three collectors at one shape, alternating: the pink one, the Gaussian
 one, and ComposedPinkCollector, pink noise from the pieces that need the host
 every step (read done, hipFFT for the finished envs, gather, given normals).
 
+--tag-sources records which policy produced every row (Collector(tag_sources=True):
+the replay's source column, a `source` key in the dataset file), for
+LAP.view / LAP.source_counts; with --bench both arms tag their rows (the loop
+arm's single-policy collectors as policy 0).
+
 usage: python tools/collect_dataset.py (--dir DIR | --stand-ins K) [--sigma S [S ...]] [--envs-per-policy 64]
-                                       [--steps 500] [--precision fp32] [--noise pink [--beta 1.0]] [--out FILE]
+                                       [--steps 500] [--precision fp32] [--noise pink [--beta 1.0]] [--tag-sources]
+                                       [--out FILE]
        python tools/collect_dataset.py --bench [--stand-ins 15] [--envs-per-policy 800] [--steps 100]
-                                       [--repeats 5] [--graph] [--noise pink] [--out FILE.json]
+                                       [--repeats 5] [--graph] [--noise pink] [--tag-sources] [--out FILE.json]
 """
 import argparse
 import ctypes
@@ -99,9 +105,10 @@ def bench(a, device):
         ag, _ = fresh_agent([n] * K, 8, prec, device)  # a ring: the timing does not need every row kept
         rb = ag.replay_buffer
         multi = Collector(PolicySet(pols, prec, device, activ), [n] * K, rb, sigma=a.sigma[0], env_kwargs=env_kw,
-                          per_policy_env_kwargs=per_kw, graph=a.graph)
+                          per_policy_env_kwargs=per_kw, graph=a.graph, tag_sources=a.tag_sources)
         singles = [SingleCollector(PolicySet([pols[k]], prec, device, activ), [n], rb, sigma=a.sigma[0],
-                                   env_kwargs=env_kw, per_policy_env_kwargs=[per_kw[k]], graph=a.graph) for k in range(K)]
+                                   env_kwargs=env_kw, per_policy_env_kwargs=[per_kw[k]], graph=a.graph,
+                                   tag_sources=a.tag_sources) for k in range(K)]
 
         def run_multi():
             multi.collect(a.steps)
@@ -231,6 +238,8 @@ def main():
     ap.add_argument("--noise", default="gaussian", choices=("gaussian", "pink"),
                     help="white Gaussian noise per policy, or one coloured sequence per env and episode")
     ap.add_argument("--beta", type=float, default=1.0, help="exponent of the coloured noise's power law (1: pink)")
+    ap.add_argument("--tag-sources", action="store_true",
+                    help="record the behaviour policy of every row (LAP.view / source_counts; a `source` key in --out)")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -257,7 +266,7 @@ def main():
     ag, _ = fresh_agent([a.envs_per_policy] * K, a.steps, a.precision, dev)
     col = Collector(PolicySet(pols, a.precision, dev, activ), a.envs_per_policy, ag.replay_buffer, sigma=sigma,
                     sigma_dec=a.sigma_dec, clip=a.clip, env_kwargs=env_kw, per_policy_env_kwargs=per_kw, seed=a.seed,
-                    graph=a.graph, noise=a.noise, beta=a.beta)
+                    graph=a.graph, noise=a.noise, beta=a.beta, tag_sources=a.tag_sources)
     try:
         torch.cuda.synchronize()
         t0 = time.time()
