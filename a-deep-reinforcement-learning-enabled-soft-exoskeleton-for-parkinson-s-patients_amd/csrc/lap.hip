@@ -1670,6 +1670,61 @@ __global__ __launch_bounds__(UPD_THREADS) void lap_view_top_kernel(float *tree, 
     }
 }
 
+// lap_views_follow: the live views of a buffer after one lap_store_batch(_src).
+// Workgroup (s, v) scans the insert's row_of: every row that landed in a real
+// slot of stratum s (not the trash row, not -1) gets view v's leaf -- the
+// view's max_priority when the row's source is kept (LAP.add's rule, on the
+// view's own maximum), else 0, which also takes an evicted kept row out of the
+// view.  The slots of one insert in one stratum are distinct (one add_batch
+// must not wrap a ring onto itself), so every leaf has one writer, and they
+// are the `cnt` ring slots that end at the ring pointer the rank kernel left:
+// their ancestors are recomputed by propagate_span, the same sums as the
+// insert's own.  kept[s] follows the change in positive leaves.
+__global__ __launch_bounds__(UPD_THREADS) void lap_views_follow_kernel(const lap_view_entry *views, int cap,
+                                                                       int levels, int capacity,
+                                                                       const int32_t *ring_ptr, const int32_t *row_of,
+                                                                       const int32_t *src, int n) {
+    const int s = blockIdx.x, t = threadIdx.x;
+    const lap_view_entry V = views[blockIdx.y];
+    // an entry cleared since the launch was recorded (a view detached, the captured
+    // insert replayed with the old n_views): nothing to follow, the whole workgroup
+    if (!V.tree || !V.max_priority || !V.kept) return;
+    float *T = stratum_tree(V.tree, s, cap);
+    __shared__ int wcnt[UPD_THREADS / 64], wdelta[UPD_THREADS / 64];
+    const float p = *V.max_priority;
+    const int row0 = s * (capacity + 1);
+    int cnt = 0, delta = 0;  // rows written, change in positive leaves
+    for (int i = t; i < n; i += UPD_THREADS) {
+        const int r = row_of[i];
+        if (r < row0 || r >= row0 + capacity) continue;
+        const int id = src ? src[i] : -1;
+        const bool kept = id >= 0 && id < V.n_keep && V.keep[id];
+        const float leaf = kept ? p : 0.0f;
+        float *L = T + cap + (r - row0);
+        delta += (leaf > 0.0f) - (*L > 0.0f);
+        *L = leaf;
+        ++cnt;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        delta += __shfl_xor(delta, o, 64);
+    }
+    if ((t & 63) == 0) {
+        wcnt[t >> 6] = cnt;
+        wdelta[t >> 6] = delta;
+    }
+    __syncthreads();
+    cnt = delta = 0;
+    for (int w = 0; w < UPD_THREADS / 64; ++w) {
+        cnt += wcnt[w];
+        delta += wdelta[w];
+    }
+    if (cnt == 0) return;  // the whole workgroup: nothing of this insert in stratum s
+    const int first = ((ring_ptr[s] - cnt) % capacity + capacity) % capacity;
+    propagate_span(T, cap, levels, capacity, first, cnt);
+    if (t == 0) V.kept[s] += delta;
+}
+
 int rc(hipError_t e) { return e == hipSuccess ? EXO_OK : EXO_EDEVICE; }
 
 int levels_of(const lap_tree_desc *t) {
@@ -1854,6 +1909,15 @@ int lap_view_build(const lap_tree_desc *view, const lap_tree_desc *base, const l
     if (hipGetLastError() != hipSuccess) return EXO_EDEVICE;
     if (cap > VIEW_LEAVES)
         hipLaunchKernelGGL(lap_view_top_kernel, dim3(view->n_strata), dim3(UPD_THREADS), 0, s, view->tree, cap);
+    return rc(hipGetLastError());
+}
+
+int lap_views_follow(const lap_tree_desc *base, const lap_storage_desc *st, const int32_t *row_ws, const int32_t *src,
+                     int32_t n, const lap_view_entry *views, int32_t n_views, void *stream) {
+    if (!valid(base) || !st || !st->ptr || !st->size || !row_ws || !views || n_views <= 0 || n < 0) return EXO_EINVAL;
+    if (n == 0) return EXO_OK;
+    hipLaunchKernelGGL(lap_views_follow_kernel, dim3(base->n_strata, n_views), dim3(UPD_THREADS), 0,
+                       (hipStream_t)stream, views, base->cap, levels_of(base), base->capacity, st->ptr, row_ws, src, n);
     return rc(hipGetLastError());
 }
 

@@ -36,6 +36,12 @@ class LapStorageDesc(ctypes.Structure):
                 ("size", c_void_p)]
 
 
+class LapViewEntry(ctypes.Structure):
+    """lap_view_entry: one live view in the device table lap_views_follow reads."""
+    _fields_ = [("tree", c_void_p), ("max_priority", c_void_p), ("keep", c_void_p), ("n_keep", c_int32),
+                ("kept", c_void_p)]
+
+
 class ExoEnvConfig(ctypes.Structure):
     """exo_env_config: the constructor arguments of ExoskeletonEnv_train
     (Environment/Exoskeleton_env.py:38-48)."""
@@ -155,6 +161,7 @@ EXPORTS = {
                                       c_void_p, ctypes.c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "lap_source_counts": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
     "lap_view_build": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    "lap_views_follow": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p]),
     "lap_store_batch_ref": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, ctypes.c_float, c_int32, c_void_p, c_void_p]),
     "lap_store_batch_ref_fused": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

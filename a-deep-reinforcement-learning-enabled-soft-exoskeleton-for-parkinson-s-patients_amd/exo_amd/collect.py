@@ -67,7 +67,10 @@ class Collector:
     (replay.enable_sources(); add_batch(source=...) with env i's policy, an
     int32 device tensor built once from seg) -- the same launches per step --
     so replay.view([p]) is policy p's dataset and replay.source_counts(K) its
-    size per stratum."""
+    size per stratum.  replay.view([p], live=True) follows the collection: the
+    insert's extra launch (lap_views_follow) is part of the step, recorded with
+    it under graph=True, and collect() records the step graphs again when views
+    were attached or detached since (replay.live_generation)."""
 
     def __init__(self, policy_set, envs_per_policy, replay, sigma=0.1, sigma_dec=0.0, clip=0.0, env_kwargs=None,
                  per_policy_env_kwargs=None, seed=0, physics="ideal", max_action=1.0, strata=None, graph=False,
@@ -144,6 +147,7 @@ class Collector:
         self.steps_run = 0
         self.use_graph = bool(graph)
         self._graphs = {}
+        self._live_gen = replay.live_generation
         policy_set.tiles(self.seg)  # the tile table and the device seg, before any capture
 
     @classmethod
@@ -199,6 +203,7 @@ class Collector:
                 self._step(c)
         cur.wait_stream(s)
         self._graphs[c] = g
+        self._live_gen = self.replay.live_generation  # the insert recorded follows this many live views
 
     def _stepped(self):
         """host bookkeeping of one step: the other buffer, the sigma schedule as set here"""
@@ -227,6 +232,10 @@ class Collector:
         with torch.cuda.device(self.device):
             self.policy_set.pack()
             k = 0
+            if self._graphs and self._live_gen != self.replay.live_generation:
+                # live views were attached to or detached from the replay since the
+                # capture: the recorded insert follows the old set, record again
+                self.release()
             if self.use_graph and len(self._graphs) < 2 and steps >= 2:
                 # each parity once eagerly (its buffers exist then), then recorded
                 self.step()
@@ -241,6 +250,7 @@ class Collector:
                     self.step()
                 else:
                     g.replay()
+                    self.replay.note_insert()  # the recorded add_batch ran: live views' pending draws are stale
                     self._stepped()
                 k += 1
         return self.report()

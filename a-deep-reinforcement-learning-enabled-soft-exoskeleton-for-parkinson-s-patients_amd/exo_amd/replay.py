@@ -88,6 +88,15 @@ class LAP:
                        torch.empty((B, 1), **f32))
         self._row_ws = None
         self.source = None  # the behaviour-policy column (enable_sources)
+        # live views (view(..., live=True)): the attached views, their lap_view_entry
+        # table on the device (allocated once: captured inserts keep its pointer),
+        # live_generation bumped by every attach / detach (a captured insert holds
+        # the number of views: Collector re-records when it moved) and
+        # insert_epoch bumped by every insert (a view's pending draw is stale then)
+        self._live = []
+        self._live_table = None
+        self.live_generation = 0
+        self.insert_epoch = 0
         self._init_tree()
 
     def _stream(self):
@@ -181,14 +190,58 @@ class LAP:
                   "lap_source_counts")
         return out
 
-    def view(self, keep, inherit=False, batch_size=None):
-        """A LapView of the rows whose source is in `keep` (see LapView)."""
-        return LapView(self, keep, inherit=inherit, batch_size=batch_size)
+    def view(self, keep, inherit=False, batch_size=None, live=False):
+        """A LapView of the rows whose source is in `keep` (see LapView).
+        live=True: the view follows this buffer's later inserts (one more
+        launch per add_batch while any view is attached) until view.detach();
+        the column is enabled if needed and strata may still be empty.  At
+        most MAX_LIVE_VIEWS (64) views are attached to one buffer at a time
+        (their device table is allocated once): ValueError beyond that."""
+        return LapView(self, keep, inherit=inherit, batch_size=batch_size, live=live)
+
+    # ------------------------------------------------------------ live views
+    MAX_LIVE_VIEWS = 64
+
+    def _live_check(self, what, attach):
+        """The one check of every attach (before anything is built) and detach."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what}: attach and detach live views eagerly, not during graph capture")
+        if attach and len(self._live) >= self.MAX_LIVE_VIEWS:
+            raise ValueError(f"{what}: at most {self.MAX_LIVE_VIEWS} live views per buffer")
+
+    def _set_live(self, views):
+        """self._live = views: the device table rewritten, the generation bumped."""
+        self._live = list(views)
+        if self._live_table is None:
+            self._live_table = torch.zeros((self.MAX_LIVE_VIEWS * ctypes.sizeof(nat.LapViewEntry),), dtype=torch.uint8,
+                                           device=self.device)
+        rows = (nat.LapViewEntry * self.MAX_LIVE_VIEWS)()  # the entries past the last view stay zero: skipped
+        for k, v in enumerate(self._live):
+            rows[k] = nat.LapViewEntry(v._tree.data_ptr(), v._maxp.data_ptr(), v._keep.data_ptr(), v._keep.numel(),
+                                       v.kept.data_ptr())
+        host = torch.frombuffer(bytearray(bytes(rows)), dtype=torch.uint8)
+        self._live_table.copy_(host)  # stream-ordered after the inserts issued so far
+        self.live_generation += 1
+
+    def note_insert(self):
+        """One more insert happened on the device without a call of add_batch:
+        a captured add_batch was replayed (Collector's step graphs)."""
+        self.insert_epoch += 1
+
+    def _inserted(self, n, source):
+        """After add_batch's two launches: the live views follow (lap_views_follow)."""
+        self.insert_epoch += 1
+        if self._live:
+            nat.check(nat.lib().lap_views_follow(ctypes.byref(self._desc), ctypes.byref(self._store),
+                                                 nat.ptr(self._row_ws), nat.ptr(source), n,
+                                                 nat.ptr(self._live_table), len(self._live), self._stream()),
+                      "lap_views_follow")
 
     def add_batch(self, state, action, next_state, reward, done, strata, active=None, source=None):
         """One vectorised env step: row i goes to stratum strata[i] (int32 [N]) if
-        active[i] (bool/uint8 [N], default all) -- lap_store_batch, two kernels,
-        no host synchronisation.  source (int32 [N] on the device, values >= 0):
+        active[i] (bool/uint8 [N], default all) -- lap_store_batch, two kernels
+        (and lap_views_follow, a third, while live views are attached), no
+        host synchronisation.  source (int32 [N] on the device, values >= 0):
         the behaviour policy of every row, into self.source by the row-copy
         launch (lap_store_batch_src, the same two kernels; the column is
         enabled if needed); without it a buffer that has the column records -1."""
@@ -207,11 +260,13 @@ class LAP:
                                                     nat.ptr(act), float(self.normalize_actions), n,
                                                     nat.ptr(self._row_ws), nat.ptr(source), nat.ptr(self.source),
                                                     self._stream()), "lap_store_batch_src")
+            self._inserted(n, source)
             return
         nat.check(nat.lib().lap_store_batch(ctypes.byref(self._desc), ctypes.byref(self._store), nat.ptr(st),
                                             nat.ptr(ac), nat.ptr(nx), nat.ptr(rw), nat.ptr(dn), nat.ptr(sr),
                                             nat.ptr(act), float(self.normalize_actions), n, nat.ptr(self._row_ws),
                                             self._stream()), "lap_store_batch")
+        self.insert_epoch += 1
 
     # ------------------------------------------------------ datasets (offline)
     def load_dataset(self, state, action, next_state, reward, done, strata, chunk=65536, source=None):
@@ -491,6 +546,10 @@ class LAP:
         if self.source is not None:
             self.source.fill_(-1)
         self._init_tree()
+        self.insert_epoch += 1
+        for v in self._live:  # every attached view empty again: zero trees, kept 0, max_priority 1
+            v._init_tree()
+            v.kept.zero_()
 
 
 class LapView(LAP):
@@ -507,17 +566,52 @@ class LapView(LAP):
     priority 1, max_priority 1; inherit=True: at the base's leaf, max_priority
     their maximum) nor written afterwards.
 
-    A view is a snapshot of the base at view() / rebuild(): rows inserted into
-    the base afterwards are not in it (a wrapped ring may even overwrite a kept
-    row with a foreign one), and inserts do not update live views.  rebuild()
-    runs the build again from the base as it is then, which also discards the
-    view's learned priorities.  ValueError if a stratum keeps no row (one host
-    read of source_counts): sample() draws from every stratum.  Inserts,
-    reset_buffer and load_dataset raise on a view."""
+    live=False: the view is a snapshot of the base at view() / rebuild(): rows
+    inserted into the base afterwards are not in it (a wrapped ring may even
+    overwrite a kept row with a foreign one).  rebuild() runs the build again
+    from the base as it is then, which also discards the view's learned
+    priorities.  ValueError if a stratum keeps no row (one host read of
+    source_counts): sample() draws from every stratum.
 
-    def __init__(self, base, keep, inherit=False, batch_size=None):
+    live=True: the view is attached to the base and follows its inserts.
+    Every add_batch / load_dataset of the base issues one more launch
+    (lap_views_follow, for all attached views together) that touches only the
+    leaves the insert wrote: a new kept row enters at the view's own
+    max_priority (LAP's rule for add; for inherit=True views too -- the base's
+    leaf is read by the build only), a foreign or untagged row gets 0, which
+    also removes a kept row the ring evicted.  The priorities the learner has
+    written to the other rows stay.  The view may be taken from an empty or
+    partly filled buffer (the column is enabled if needed): self.kept (int32
+    [E], on the device) counts the rows with a positive leaf per stratum and
+    ready() -- one host read -- says whether every stratum keeps one; sample
+    only then.  kept moves with inserts only: priorities written to a live view
+    must be > 0 (TD7's are, min_priority ** alpha at least), a 0 would hide the
+    row while kept still counts it.  A view that keeps no row when it is built
+    starts at max_priority 1, with inherit=True too (the inherit build's
+    maximum over no leaf is replaced by LAP's initial value).
+    If reset_max_priority runs on a view that keeps no row its
+    max_priority is 0 until the next update_priority, and rows inserted
+    meanwhile are not reachable.  base.reset_buffer() empties the attached
+    views with it.  detach() ends the following: the view is a snapshot from
+    then on.  Attach and detach eagerly, never during graph capture; a captured
+    add_batch holds the number of attached views (Collector re-records its
+    step graphs when base.live_generation moved).
+
+    A draw made before an insert may name a slot that now holds another row:
+    `stale` is true when the base has taken rows since this view last sampled,
+    and update_priority / update_priority_and_sample(_td) raise ValueError for
+    the view's own index buffer of such a draw (writing a priority there could
+    make a foreign row reachable).  Sample again instead; dropping a pending
+    draw is harmless, its rows keep their priorities.
+
+    Inserts, reset_buffer and load_dataset raise on a view."""
+
+    def __init__(self, base, keep, inherit=False, batch_size=None, live=False):
         if isinstance(base, LapView):
             raise ValueError("LAP.view: take the view from the base buffer")
+        if live:
+            base._live_check("LAP.view(live=True)", attach=True)  # before anything is built
+            base.enable_sources()
         if base.source is None:
             raise ValueError("LAP.view: the buffer has no source column (enable_sources / add_batch(source=...))")
         keep = sorted({int(k) for k in keep})
@@ -547,18 +641,89 @@ class LapView(LAP):
         sn = torch.empty((2, B, self.state_dim), **f32)
         self._batch = (sn[0], torch.empty((B, self.action_dim), **f32), sn[1], torch.empty((B, 1), **f32),
                        torch.empty((B, 1), **f32))
+        self.kept = torch.zeros((E,), **i32)  # rows with a positive leaf, per stratum
+        self.live = bool(live)
+        self._drawn = {}   # index buffer -> the base's insert epoch at its draw (live views)
+        self._seen = None  # the insert epoch at the last draw
         self.rebuild()
+        if self.live:
+            base._set_live(base._live + [self])
 
     def rebuild(self):
-        """Build the view's trees again from the base as it is now."""
+        """Build the view's trees again from the base as it is now (kept with
+        them); a live view stays attached."""
         counts = self.base.source_counts(self._keep.numel())[:, :-1].cpu()
-        empty = (counts[:, self.keep].sum(1) == 0).nonzero().reshape(-1).tolist()
-        if empty:
+        kept = counts[:, self.keep].sum(1)
+        empty = (kept == 0).nonzero().reshape(-1).tolist()
+        if empty and not self.live:
             raise ValueError(f"LAP.view: no rows of sources {self.keep} in strata {empty} (every stratum is sampled)")
+        self.kept.copy_(kept.to(torch.int32))
         nat.check(nat.lib().lap_view_build(ctypes.byref(self._desc), ctypes.byref(self.base._desc),
                                            ctypes.byref(self._store), nat.ptr(self.source), nat.ptr(self._keep),
                                            self._keep.numel(), int(self.inherit), self._stream()), "lap_view_build")
+        if self.inherit and int(kept.sum()) == 0:
+            # the inherit build leaves max_priority = the largest kept leaf, 0 when no
+            # row is kept yet (a live view of an empty buffer): LAP's initial 1 instead,
+            # or every row that enters later would get the leaf 0
+            self._maxp.fill_(1.0)
         return self
+
+    def ready(self):
+        """Every stratum keeps at least one row (one host read of self.kept)."""
+        return bool((self.kept > 0).all())
+
+    def detach(self):
+        """End the following: the view is a snapshot of the base from now on."""
+        if self.live:
+            self.base._live_check("LapView.detach", attach=False)
+            self.base._set_live([v for v in self.base._live if v is not self])
+            self.live = False
+            self._drawn, self._seen = {}, None
+        return self
+
+    # ------------------------------------------------------ pending draws
+    @property
+    def stale(self):
+        """The base has taken rows since this live view last sampled."""
+        return self.live and self._seen is not None and self._seen != self.base.insert_epoch
+
+    def note_draw(self, slot=None):
+        """The batch slot was drawn into just now without a call of sample():
+        a captured update_priority_and_sample was replayed (OfflineTrainer)."""
+        self._note(self._slot(slot)[1])
+
+    def _note(self, idx):
+        if self.live:
+            self._seen = self._drawn[idx.data_ptr()] = self.base.insert_epoch
+
+    def _fresh(self, ind, what):
+        ind = self.ind if ind is None else ind
+        if self.live and ind is not None and self._drawn.get(ind.data_ptr(), self.base.insert_epoch) != \
+                self.base.insert_epoch:
+            raise ValueError(f"LapView.{what}: the base has taken rows since these indices were drawn (the slots may "
+                             "hold other rows now): sample() again")
+        return ind
+
+    def sample(self, slot=None):
+        batch = super().sample(slot)
+        self._note(self.ind)
+        return batch
+
+    def update_priority(self, priority, ind=None):
+        super().update_priority(priority, self._fresh(ind, "update_priority"))
+
+    def update_priority_and_sample(self, priority, ind=None, slot=None, before_gather=None):
+        batch = super().update_priority_and_sample(priority, self._fresh(ind, "update_priority_and_sample"), slot,
+                                                   before_gather)
+        self._note(self.ind)
+        return batch
+
+    def update_priority_and_sample_td(self, td, alpha, min_priority, ind, slot, prio_out=None):
+        batch = super().update_priority_and_sample_td(td, alpha, min_priority,
+                                                      self._fresh(ind, "update_priority_and_sample_td"), slot,
+                                                      prio_out)
+        self._note(self.ind)
+        return batch
 
     def _not_on_a_view(self, *a, **k):
         raise ValueError("LapView: a view is read-only storage (insert into, reset or load the base buffer, "

@@ -1705,6 +1705,13 @@ class OfflineTrainer:
     new_graph / capture, and retire_graphs(trainer) (= release_graphs()) when
     done ("The graph-replay crash").  One GPU only.
 
+    On a live view (LAP.view(..., live=True) through Agent.use_replay) the
+    trainer can alternate with a Collector that fills the view's base: when
+    the base took rows since the pending batch was drawn, step() first draws
+    that batch again (one eager lap_sample_gather into the slot's static
+    buffers, so the graphs stay valid; counted in self.resamples; one small
+    host read, view.ready(), on this path only).  The learned priorities stay.
+
     Not here: the overlapped pairs, the target prefetch and the
     encoder step on its branch (TD7Learner.defer_side_join) of VecTrainer."""
 
@@ -1720,8 +1727,12 @@ class OfflineTrainer:
         self.iters = 0
         self.refreshes = 0
         self._slot = 0
+        self.resamples = 0  # batches drawn again because a live view's base took rows
         rb = agent.replay_buffer
-        if int((rb.size_s == 0).sum()):
+        if getattr(rb, "live", False):
+            if not rb.ready():
+                raise ValueError("OfflineTrainer: a stratum of the live view keeps no row yet (collect first)")
+        elif int((rb.size_s == 0).sum()):
             raise ValueError("OfflineTrainer: a stratum of the replay is empty (load a dataset first)")
         if self.use_graphs:
             graph_reductions_ok(self.device)
@@ -1785,6 +1796,16 @@ class OfflineTrainer:
     def step(self):
         """One Agent.train() (TD7_multi_agent.py:211-293)."""
         ag, L = self.agent, self.agent.learner
+        rb = ag.replay_buffer
+        live = getattr(rb, "live", False)
+        if live and rb.stale:
+            # the base took rows since the pending batch was drawn: its slots may
+            # hold other rows now.  One eager launch into the same static buffers
+            # (the captured graphs stay valid); the dropped draw costs nothing.
+            if not rb.ready():
+                raise RuntimeError("OfflineTrainer: a stratum of the live view keeps no row any more")
+            rb.sample(slot=self._slot)
+            self.resamples += 1
         L.training_steps += 1
         update_actor = L.training_steps % ag.hp.policy_freq == 0
         key = (update_actor, self._slot)
@@ -1795,6 +1816,8 @@ class OfflineTrainer:
             if key not in self.graphs:
                 self._capture(key)
             self.graphs[key].replay()
+            if live:
+                rb.note_draw(1 - self._slot)  # the replayed update_priority_and_sample drew it
         self._slot ^= 1
         self._refresh_targets()
         self.iters += 1

@@ -382,6 +382,33 @@ int lap_view_build(const lap_tree_desc *view, const lap_tree_desc *base, const l
                    const int32_t *source_dev, const uint8_t *keep_dev, int32_t n_keep, int32_t inherit,
                    void *stream);
 
+/* One live view of a buffer, as lap_views_follow reads it from a device table:
+ * the view's trees and max_priority (a lap_tree_desc's, with the base's
+ * n_strata / capacity / cap), its keep table (lap_view_build's keep_dev /
+ * n_keep) and kept_dev[n_strata] (int32), the view's count of rows with a
+ * positive leaf per stratum. */
+typedef struct {
+    float *tree;
+    float *max_priority;
+    const uint8_t *keep;
+    int32_t n_keep;
+    int32_t *kept;
+} lap_view_entry;
+
+/* The views of views_dev[n_views] follow one insert: issued after
+ * lap_store_batch_src (or lap_store_batch on a buffer with the column) with
+ * that call's n, row_ws_dev and src_dev (NULL: the rows are untagged) and the
+ * base's descriptors.  In every view the leaf of each slot the insert wrote
+ * becomes the view's max_priority when the row's source is kept, else 0 (a
+ * kept row evicted by a foreign one leaves the view), the ancestors of the
+ * insert's ring span are recomputed (T[2n] + T[2n+1] in fp32, the sums
+ * lap_view_build computes for the same leaves) and kept_dev[s] moves by the
+ * change in positive leaves.  One launch, grid (n_strata, n_views); nothing
+ * is launched for n == 0.  The base's tree is neither read nor written. */
+int lap_views_follow(const lap_tree_desc *base, const lap_storage_desc *st, const int32_t *row_ws_dev,
+                     const int32_t *src_dev, int32_t n, const lap_view_entry *views_dev, int32_t n_views,
+                     void *stream);
+
 /* LAP.add (Agent/TD7_buffer_multi_agent.py:49-63) called once per active env
  * of one vectorised step, in env order -- the training script's per-env loop
  * (Simulation/Exoskeleton_agent_train.py:139-142) -- with the reference's
